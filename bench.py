@@ -6,9 +6,19 @@ on synthetic order-book-shaped data (random-init weights), on N GPUs of one
 node (weak scaling: per-GPU batch fixed).
 
     python bench.py --gpus N --steps K --warmup W [--config repo]
+                    [--dump-outputs DIR] [--full]
 
 Launched by torchrun for N > 1 (reads RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*).
 Rank 0 prints exactly one JSON line.
+
+A plain run sets up, warms up, times exactly K steps and prints the result
+line. --dump-outputs DIR additionally writes what the last timed step
+computed as DIR/<name>.npy (float32, at most 64 MB in all). --full adds the
+measurements that need steps of their own after the timed region (the
+averaged 3-class accuracy snapshot, `train_3class_acc` in the result line).
+The `metric` string names both halves, "train seq/sec + 3-class acc", in
+every run; `value` is always the seq/sec half, and the accuracy half is
+reported only with --full.
 
 The timed step is the full reference training step (biGRU_model.py:162-210):
 dropout -> biGRU forward -> 3-way pooled head -> BCEWithLogitsLoss(weight,
@@ -35,6 +45,28 @@ def three_class_accuracy(target: torch.Tensor, pred: torch.Tensor) -> float:
     return float(_acc3(target, pred))
 
 
+# payload budget of --dump-outputs; with the .npy headers the directory
+# stays under 64 MB (64e6 bytes)
+DUMP_BUDGET_BYTES = 56 * 2 ** 20
+
+
+def dump_outputs(outdir: str, tensors: dict) -> None:
+    """Write each tensor as outdir/<name>.npy in float32. The byte budget is
+    split evenly; a tensor over its share is stored as a fixed, seeded sample
+    of its flattened elements (same indices every run), so two builds can be
+    compared output for output."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (4 * max(len(tensors), 1))
+    for name, t in tensors.items():
+        a = t.detach().to(device="cpu", dtype=torch.float32)
+        if a.numel() > share:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(a.numel(), generator=g)[:share].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, f"{name}.npy"), a.contiguous().numpy())
+
+
 def bench_predict(cfg, args, use_cuda):
     """BASELINE.json configs[4]: batch=1 streaming inference p50 latency,
     hipGraph-captured step on GPU."""
@@ -53,23 +85,27 @@ def bench_predict(cfg, args, use_cuda):
     g = torch.Generator().manual_seed(1)
     for _ in range(cfg.seq_len):
         pred.push_row(torch.rand(cfg.n_features, generator=g))
-    for _ in range(max(args.warmup, 3)):
+    for _ in range(args.warmup):
         pred.predict_window()
     if use_cuda:
         torch.cuda.synchronize()
     lats = []
-    for i in range(max(args.steps, 50)):
+    out = None
+    for i in range(args.steps):
         pred.push_row(torch.rand(cfg.n_features, generator=g))
         t0 = time.perf_counter()
-        pred.predict_window()
+        out = pred.predict_window()
         if use_cuda:
             torch.cuda.synchronize()
         lats.append((time.perf_counter() - t0) * 1000.0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {
+            "probabilities": torch.tensor(out["probabilities"])})
     p50 = float(np.percentile(lats, 50))
     result = {
         "metric": "p50 batch=1 streaming predict latency",
         "value": p50, "unit": "ms", "n_gpus": 1 if use_cuda else 0,
-        "steps": len(lats), "warmup": max(args.warmup, 3),
+        "steps": len(lats), "warmup": args.warmup,
         "ms_per_step": p50, "higher_is_better": False, "scaling": "weak",
         "vs_baseline": None,
         "dtype": "bf16" if dtype == torch.bfloat16 else "fp32",
@@ -96,7 +132,16 @@ def main():
                     help="gradient sync mode (default: bucketed; fused for "
                          "the stress config, whose 64 MB payload would "
                          "otherwise split into ~64 latency-bound collectives)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (loss, logits, "
+                         "updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that need steps of their "
+                         "own (3-class accuracy snapshot after the timed "
+                         "region)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # --gpus documents the intended N; the actual world size comes from the
@@ -166,6 +211,7 @@ def main():
     acc_sum = torch.zeros((), device=device)
     acc3_sum = 0.0
     n_acc = 0
+    last_out = [None, None]  # (loss, logits) of the most recent step
 
     # Optional roctx ranges (FMDA_ROCTX=1): torch's nvtx API emits roctx
     # markers on ROCm, letting `rocprofv3 --marker-trace` segment the step
@@ -212,6 +258,9 @@ def main():
         if measure_quality:
             acc3_sum += three_class_accuracy(y, pred)
         n_acc += 1
+        # what a caller of the step receives; kept for --dump-outputs
+        # (detach is a view: no kernel, no sync)
+        last_out[0], last_out[1] = loss.detach(), logits.detach()
 
     model.train()
     for i in range(args.warmup):
@@ -236,9 +285,18 @@ def main():
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     dt_max = float(dt.item())
 
-    # quality snapshot (outside the timed region), averaged over several
-    # steps — a single step's 3-class accuracy is too noisy for a headline
-    n_quality = 4
+    # the last timed step's results: loss, logits and the parameters it
+    # updated in place (rank 0's shard of the batch under data parallelism)
+    if args.dump_outputs and rank == 0:
+        outs = {"loss": last_out[0], "logits": last_out[1]}
+        for name, p in model.named_parameters():
+            outs[f"param.{name}"] = p
+        dump_outputs(args.dump_outputs, outs)
+
+    # --full: quality snapshot (outside the timed region), averaged over
+    # several steps — a single step's 3-class accuracy is too noisy for a
+    # headline
+    n_quality = 4 if args.full else 0
     for i in range(n_quality):
         step(i, measure_quality=True)
     acc = float(acc_sum.item()) / max(n_acc, 1)
@@ -267,9 +325,10 @@ def main():
                 "parallelism": f"dp{n_gpus}",
                 "bench_config": cfg_name,
                 "train_subset_acc": acc,
-                "train_3class_acc": acc3_sum / n_quality,
             },
         }
+        if args.full:
+            result["config"]["train_3class_acc"] = acc3_sum / n_quality
         print(json.dumps(result))
 
     if dist is not None:

@@ -79,6 +79,11 @@ extern "C" int fmda_head_bwd_launch(int is_bf16, const float* sig,
                                     const float* pw, const float* gscale,
                                     const void* W, float* dlogits, void* dx,
                                     int B, int K, int C, hipStream_t stream);
+extern "C" int fmda_gru_bwd_db_rows(int is_bf16, int Hp, int B,
+                                    int column_split);
+extern "C" int fmda_gru_db_reduce_launch(const float* part, int rows,
+                                         int n_dir, int Hp, float* dbhh,
+                                         float* dbih, hipStream_t stream);
 extern "C" int fmda_opt_norm2_launch(const void* chunks, int n_chunks,
                                      float* out, hipStream_t stream);
 namespace fmda_ckpt {
@@ -236,8 +241,15 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
                             gi.options().dtype(torch::kFloat32));
     // packed bias-grad sums: [dr, dz, dhn | dn] per direction; db_hh and
     // db_ih are assembled from slices below (dr/dz shared).
-    auto dbsum = torch::zeros({n_dir, 4 * Hp},
-                              gi.options().dtype(torch::kFloat32));
+    // Each batch tile of the launch stores its sums into a row of its own
+    // and the rows are summed below in a fixed order, which keeps the bias
+    // grads bitwise reproducible. The launcher reports how many rows its
+    // grid writes for this shape.
+    const bool column_split = is_bf16 && Hp == 512 && h0 == nullptr;
+    const int64_t db_rows = fmda_gru_bwd_db_rows(is_bf16 ? 1 : 0, Hp, B,
+                                                 column_split ? 1 : 0);
+    auto dbpart = torch::zeros({db_rows, n_dir, 4 * Hp},
+                               gi.options().dtype(torch::kFloat32));
     // W^T for the carry GEMM's B fragments (v3 kernel streams them from
     // L2 as contiguous bf16x8 rows instead of hoisting 48 VGPRs).
     torch::Tensor wt;
@@ -248,7 +260,7 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
     }
     auto stream = at::hip::getCurrentHIPStream();
     int rc;
-    if (is_bf16 && Hp == 512 && h0 == nullptr) {
+    if (column_split) {
         const unsigned int cs_thr =
             (drop_p > 0.0) ? (unsigned int)((float)drop_p * 256.0f) : 0u;
         const float cs_scale =
@@ -262,7 +274,7 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
             gi.data_ptr(), w.data_ptr(), wt_ptr, bhh.data_ptr<float>(),
             out.data_ptr(), dout.data_ptr(), dhT.data_ptr<float>(),
             dgi.data_ptr(), dgh.data_ptr(), dh0.data_ptr<float>(),
-            dbsum.data_ptr<float>(), gpub.data_ptr(),
+            dbpart.data_ptr<float>(), gpub.data_ptr(),
             (unsigned int*)cnt.data_ptr(), B, T, n_dir, cs_thr, cs_scale,
             (unsigned long long)drop_seed, stream.stream());
     } else {
@@ -284,19 +296,24 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
                                  out.data_ptr(), dout.data_ptr(),
                                  dhT.data_ptr<float>(), dgi.data_ptr(),
                                  dgh.data_ptr(), dh0.data_ptr<float>(),
-                                 dbsum.data_ptr<float>(), B, T,
+                                 dbpart.data_ptr<float>(), B, T,
                                  n_dir, drop_thr, drop_scale,
                                  (unsigned long long)drop_seed, h0, dgh0_ptr,
                                  stream.stream());
     }
     TORCH_CHECK(rc == 0, "fmda gru_bwd launch failed rc=", rc, " Hp=", Hp);
-    using torch::indexing::Slice;
-    auto dbhh = dbsum.index({Slice(), Slice(0, 3 * Hp)});
-    auto dbih = torch::cat({dbsum.index({Slice(), Slice(0, 2 * Hp)}),
-                            dbsum.index({Slice(), Slice(3 * Hp, 4 * Hp)})}, 1);
+    // fixed-order row sum + slot scatter: db_hh = [dr, dz, dhn],
+    // db_ih = [dr, dz, dn] (dr/dz shared); every element is written
+    auto dbhh = torch::empty({n_dir, 3 * Hp},
+                             gi.options().dtype(torch::kFloat32));
+    auto dbih = torch::empty_like(dbhh);
+    rc = fmda_gru_db_reduce_launch(dbpart.data_ptr<float>(), (int)db_rows,
+                                   n_dir, Hp, dbhh.data_ptr<float>(),
+                                   dbih.data_ptr<float>(), stream.stream());
+    TORCH_CHECK(rc == 0, "fmda gru db reduce launch failed");
     if (dgh0_ptr != nullptr)
-        return {dgi, dgh, dh0, dbhh.contiguous(), dbih, dgh0};
-    return {dgi, dgh, dh0, dbhh.contiguous(), dbih};
+        return {dgi, dgh, dh0, dbhh, dbih, dgh0};
+    return {dgi, dgh, dh0, dbhh, dbih};
 }
 
 torch::Tensor mfma_selftest(torch::Tensor A, torch::Tensor Bm) {
@@ -355,13 +372,20 @@ torch::Tensor fused_clip_adam(torch::Tensor chunks, int64_t n_chunks,
                               double clip, double lr, double beta1,
                               double beta2, double eps, int64_t step) {
     TORCH_CHECK(chunks.is_cuda() && chunks.scalar_type() == torch::kInt64);
-    auto norm2 = torch::zeros({1}, chunks.options().dtype(torch::kFloat32));
+    auto f32 = chunks.options().dtype(torch::kFloat32);
+    torch::Tensor norm2;
     auto stream = at::hip::getCurrentHIPStream();
     if (clip > 0) {
+        // one partial per block of the launch grid (min(n_chunks, 2048)
+        // blocks, every block stores its entry), summed in a fixed order
+        auto part = torch::empty({std::min<int64_t>(n_chunks, 2048)}, f32);
         int rc = fmda_opt_norm2_launch(chunks.data_ptr(), (int)n_chunks,
-                                       norm2.data_ptr<float>(),
+                                       part.data_ptr<float>(),
                                        stream.stream());
         TORCH_CHECK(rc == 0, "opt norm2 launch failed");
+        norm2 = part.sum().reshape({1});
+    } else {
+        norm2 = torch::zeros({1}, f32);
     }
     const float bc1 = 1.0f - powf((float)beta1, (float)step);
     const float bc2 = 1.0f - powf((float)beta2, (float)step);
@@ -382,15 +406,17 @@ std::vector<torch::Tensor> head_loss_fwd(torch::Tensor x, torch::Tensor W,
     auto f32 = x.options().dtype(torch::kFloat32);
     auto logits = torch::empty({B, C}, f32);
     auto sig = torch::empty({B, C}, f32);
-    auto loss = torch::zeros({1}, f32);
+    // one partial per block of the launch grid ((B*C + 255) / 256 blocks,
+    // every block stores its entry), summed here in a fixed order
+    auto part = torch::empty({((int64_t)B * C + 255) / 256}, f32);
     auto stream = at::hip::getCurrentHIPStream();
     int rc = fmda_head_fwd_launch(
         bf16 ? 1 : 0, x.data_ptr(), W.data_ptr(), b.data_ptr(),
         y.data_ptr<float>(), wgt.data_ptr<float>(), pw.data_ptr<float>(),
         logits.data_ptr<float>(), sig.data_ptr<float>(),
-        loss.data_ptr<float>(), B, K, C, stream.stream());
+        part.data_ptr<float>(), B, K, C, stream.stream());
     TORCH_CHECK(rc == 0, "head fwd launch failed");
-    return {logits, sig, loss};
+    return {logits, sig, part.sum().reshape({1})};
 }
 
 std::vector<torch::Tensor> head_loss_bwd(torch::Tensor sig, torch::Tensor y,

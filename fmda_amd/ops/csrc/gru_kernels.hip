@@ -28,8 +28,8 @@
 //   dW_ih/db_ih/dx) and dGh. dGh is stored TIME-SHIFTED so that slot t holds
 //   the gate grads whose h_prev is out[t]: dW_hh then reduces with a single
 //   contiguous rocBLAS GEMM (dgh^T @ out), no sliced copies. db_hh is
-//   accumulated in-kernel (registers across T, one atomicAdd per column per
-//   block).
+//   accumulated in-kernel (registers across T, one store per column into the
+//   block's own row of a partials table, summed in a fixed order afterwards).
 // - fp32 instantiations use a plain VALU dot-product path with the same
 //   phase structure and C-tile ownership; they are the on-GPU numerics
 //   oracle, validated against the PyTorch fp32 reference.
@@ -842,8 +842,12 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
     }
 
     // bias grads: reduce the 4 row-quarter lanes (same j = lane&15), then
-    // one atomicAdd per (slot, column) per block. dbhh layout (n_dir, 4Hp):
+    // one store per (slot, column) into THIS batch tile's row of the
+    // partials table — (batch tile, n_dir, 4Hp), summed over tiles by the
+    // host in a fixed order, so the result is bitwise reproducible (a
+    // float atomicAdd across blocks is not). Row layout (n_dir, 4Hp):
     // [dr, dz, dhn | dn] — db_hh = slots 0..2, db_ih = slots 0,1,3.
+    float* dbrow = dbhh + ((long)blockIdx.x * n_dir + dir) * 4 * Hp;
 #pragma unroll
     for (int i = 0; i < CPW; ++i) {
         const int ct = wave + NW * i;
@@ -854,8 +858,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
             v += __shfl_xor(v, 16);
             v += __shfl_xor(v, 32);
             if ((lane >> 4) == 0)
-                atomicAdd(&dbhh[(long)dir * 4 * Hp + g * Hp + ct * 16 +
-                                (lane & 15)], v);
+                dbrow[g * Hp + ct * 16 + (lane & 15)] = v;
         }
     }
 }
@@ -1752,14 +1755,18 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
                 }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                // dbhh layout (n_dir, 4Hp): [dr, dz, dhn | dn] — db_hh =
-                // slots 0..2, db_ih = slots 0,1,3 (assembled host-side).
+                // one store into this batch tile's row of the partials
+                // table (batch tile, n_dir, 4Hp); the host sums the tiles
+                // in a fixed order (bitwise reproducible, unlike a float
+                // atomicAdd across blocks). Row layout (n_dir, 4Hp):
+                // [dr, dz, dhn | dn] — db_hh = slots 0..2, db_ih = slots
+                // 0,1,3 (assembled host-side).
                 float v = dbacc[i][g];
                 v += __shfl_xor(v, 16);
                 v += __shfl_xor(v, 32);
                 if ((lane >> 4) == 0)
-                    atomicAdd(&dbhh[(long)dir * 4 * Hp + g * Hp + ct * 16 +
-                                    (lane & 15)], v);
+                    dbhh[((long)blockIdx.x * n_dir + dir) * 4 * Hp + g * Hp +
+                         ct * 16 + (lane & 15)] = v;
             }
         }
     }
@@ -2493,9 +2500,15 @@ void gru_bwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
                 }
         }
         // packed bias sums: per j-tile column, reduce the row-quarter
-        // lanes and emit one atomic per (slot, column); dbhh layout is
-        // (n_dir, 4Hp) = [dr | dz | dhn | dn] (db_hh / db_ih assembled
-        // host-side exactly as for the Hp=128 kernels).
+        // lanes and emit one store per (slot, column). The waves of a
+        // block split the batch rows, so each (batch group, wave) owns a
+        // row of the partials table — (gb * NW + wave, n_dir, 4Hp) — and
+        // the host sums the rows in a fixed order (bitwise reproducible,
+        // unlike float atomics). Row layout (n_dir, 4Hp) = [dr | dz | dhn
+        // | dn] (db_hh / db_ih assembled host-side exactly as for the
+        // Hp=128 kernels).
+        float* dbrow =
+            dbhh + (((long)gb * NW + wave) * n_dir + dir) * 4 * Hp;
 #pragma unroll
         for (int j = 0; j < JT; ++j)
 #pragma unroll
@@ -2504,8 +2517,7 @@ void gru_bwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
                 v += __shfl_xor(v, 16);
                 v += __shfl_xor(v, 32);
                 if ((lane >> 4) == 0)
-                    atomicAdd(&dbhh[(long)dir * 4 * Hp + q4 * Hp + ct * CS +
-                                    j * 16 + (lane & 15)], v);
+                    dbrow[q4 * Hp + ct * CS + j * 16 + (lane & 15)] = v;
             }
     }
 }
@@ -3023,8 +3035,8 @@ extern "C" int fmda_head_sigmoid_launch(int is_bf16, const void* x,
 // BCEWithLogitsLoss(weight, pos_weight) (cell 29) forward/backward chain
 // (~12 eager launches) with:
 //   fwd: logits = x @ W^T + b; s = sigmoid(logits); per-element loss
-//        l = -w[ pw*y*log(s) + (1-y)*log(1-s) ], mean-reduced to a scalar
-//        by block partials + one atomicAdd. C = #classes (4), 3H small.
+//        l = -w[ pw*y*log(s) + (1-y)*log(1-s) ], reduced to one partial
+//        per block (summed host-side). C = #classes (4), 3H small.
 //   bwd: dlogits = gscale * w[ s(1 - y + pw*y) - pw*y ];
 //        dx = dlogits @ W (tiny K) in one elementwise-ish kernel.
 //   (dW/db reduce over B on the host via the split-K helpers.)
@@ -3061,7 +3073,9 @@ __global__ void head_loss_fwd_kernel(const T* __restrict__ x,
         const float log_1ms = -lse;         // log(1 - sigmoid(acc))
         l = -wgt[c] * (pw[c] * yy * log_s + (1.0f - yy) * log_1ms);
     }
-    // block-reduce partials, one atomic per block
+    // block-reduce partials, one store per block into loss_sum[blockIdx.x]
+    // (gridDim.x entries); the host sums them in a fixed order, so the loss
+    // is bitwise reproducible (a float atomicAdd across blocks is not)
     __shared__ float red[4];
     float v = l;
     v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
@@ -3071,7 +3085,7 @@ __global__ void head_loss_fwd_kernel(const T* __restrict__ x,
     if (threadIdx.x == 0) {
         float t = 0.0f;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-        atomicAdd(loss_sum, t);
+        loss_sum[blockIdx.x] = t;
     }
 }
 
@@ -3339,6 +3353,14 @@ static int launch_bwd_v3_128_t(const void* gi, const void* w, const void* wt,
     return 0;
 }
 
+// FMDA_BWD_BT16 A/B switch, latched once per process: the launcher's tile
+// size and the partials-table row count (fmda_gru_bwd_db_rows) both read it
+// here, so they can never disagree.
+static bool bwd_v3_bt16() {
+    static const bool small = getenv("FMDA_BWD_BT16") != nullptr;
+    return small;
+}
+
 static int launch_bwd_v3_128(const void* gi, const void* w, const void* wt,
                              const float* bhh,
                              const void* out, const void* dout,
@@ -3352,8 +3374,7 @@ static int launch_bwd_v3_128(const void* gi, const void* w, const void* wt,
     // independent serial chains hide each other's latencies; MT=1 halves
     // the per-lane accumulator footprint. ~80 KB dynamic LDS per block,
     // 2x just fits the 160 KB CU budget.
-    static const bool small = getenv("FMDA_BWD_BT16") != nullptr;
-    if (small)
+    if (bwd_v3_bt16())
         return launch_bwd_v3_128_t<16, 256>(
             gi, w, wt, bhh, out, dout, dhT, dgi, dgh, dh0, dbhh, B, Tseq,
             n_dir, drop_thr, drop_scale, drop_seed, h0, dgh0, stream);
@@ -3478,6 +3499,62 @@ extern "C" int fmda_gru_bwd_cs_launch(const void* gi, const void* w,
         (const __hip_bfloat16*)dout, dhT, (__hip_bfloat16*)dgi,
         (__hip_bfloat16*)dgh, dh0, dbhh, (__hip_bfloat16*)gpub, cnt, B,
         Tseq, n_dir, GB, drop_thr, drop_scale, drop_seed);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Rows of the bias-grad partials table (rows, n_dir, 4Hp) that the backward
+// launch for this shape writes: one per batch tile (grid.x of the
+// batch-parallel kernels), or one per (256-row batch group, wave) for the
+// column-split kernel (BR = 256, NT = 512 -> 8 waves).
+extern "C" int fmda_gru_bwd_db_rows(int is_bf16, int Hp, int B,
+                                    int column_split) {
+    if (column_split) return 8 * ((B + 255) / 256);
+    int bt = bwd_cfg(is_bf16, Hp).bt;
+    if (is_bf16 && Hp == 128 && bwd_v3_bt16()) bt = 16;
+    return (B + bt - 1) / bt;
+}
+
+// Sums the partials table (rows, n_dir, 4Hp) over rows in a fixed order and
+// scatters the packed slots [dr, dz, dhn | dn] straight into db_hh (slots
+// 0..2) and db_ih (slots 0,1,3), both (n_dir, 3Hp). 64 columns per block,
+// DB_RG waves striding the rows, combined through LDS in wave order.
+constexpr int DB_RG = 16;
+__global__ void db_reduce_kernel(const float* __restrict__ part, int rows,
+                                 int n_dir, int Hp,
+                                 float* __restrict__ dbhh,
+                                 float* __restrict__ dbih) {
+    __shared__ float red[DB_RG][64];
+    const int ncol = n_dir * 4 * Hp;
+    const int col = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int rg = threadIdx.x >> 6;
+    float s = 0.0f;
+    if (col < ncol) {
+        // independent loads issued ahead of the (ordered) adds
+#pragma unroll 8
+        for (int r = rg; r < rows; r += DB_RG)
+            s += part[(long)r * ncol + col];
+    }
+    red[rg][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (rg == 0 && col < ncol) {
+        float t = red[0][threadIdx.x];
+#pragma unroll
+        for (int k = 1; k < DB_RG; ++k) t += red[k][threadIdx.x];
+        const int dir = col / (4 * Hp);
+        const int g = (col % (4 * Hp)) / Hp;
+        const int j = col % Hp;
+        if (g < 3) dbhh[(long)dir * 3 * Hp + g * Hp + j] = t;
+        if (g != 2)
+            dbih[(long)dir * 3 * Hp + (g == 3 ? 2 : g) * Hp + j] = t;
+    }
+}
+
+extern "C" int fmda_gru_db_reduce_launch(const float* part, int rows,
+                                         int n_dir, int Hp, float* dbhh,
+                                         float* dbih, hipStream_t stream) {
+    const int ncol = n_dir * 4 * Hp;
+    db_reduce_kernel<<<dim3((ncol + 63) / 64), 64 * DB_RG, 0, stream>>>(
+        part, rows, n_dir, Hp, dbhh, dbih);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

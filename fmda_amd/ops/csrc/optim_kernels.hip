@@ -3,7 +3,8 @@
 // Replaces the reference's clip_grad_norm_(params, clip) + Adam.step()
 // (biGRU_model.py:208-210, notebook cell 29) with two launches over a
 // packed chunk table:
-//   1) global L2 norm^2 of all grads (block partials -> one atomicAdd)
+//   1) global L2 norm^2 of all grads (one partial per block, summed by the
+//      caller in a fixed order: bitwise reproducible, unlike atomicAdd)
 //   2) Adam update with the clip scale min(1, clip/norm) folded into the
 //      gradient read; m/v/param updated in one pass (fp32 masters).
 // The chunk table lives in a single device buffer: per chunk
@@ -46,7 +47,7 @@ __global__ void norm2_kernel(const OptChunk* __restrict__ chunks, int n_chunks,
     if (threadIdx.x == 0) {
         float t = 0.0f;
         for (int w = 0; w < OPT_NT / 64; ++w) t += red[w];
-        atomicAdd(out, t);
+        out[blockIdx.x] = t;  // gridDim.x partials, summed by the caller
     }
 }
 

@@ -17,6 +17,9 @@ import pytest
 def test_bench_under_torchrun_cpu(world, port):
     env = dict(os.environ)
     env["MASTER_ADDR"] = "127.0.0.1"
+    # CPU/gloo by design: hide any GPU from the ranks, or on a GPU box with
+    # fewer than `world` devices rank 1 would fail in set_device(local_rank)
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "-1"
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",

@@ -1,3 +1,4 @@
+import os
 import pickle
 
 import torch
@@ -15,7 +16,8 @@ def test_registry_is_108_columns():
 def test_registry_matches_reference_norm_params_order():
     """Column order must equal the reference norm_params artifact
     (predict.py:110-122 relies on dict insertion order)."""
-    with open("/root/reference/norm_params", "rb") as f:
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                           "golden", "reference_norm_params"), "rb") as f:
         ref = pickle.load(f)
     assert list(ref.keys()) == FEATURE_NAMES
     for name in FEATURE_NAMES:

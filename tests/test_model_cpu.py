@@ -1,3 +1,5 @@
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -5,7 +7,8 @@ import torch.nn as nn
 from fmda_amd.models import BiGRU, load_checkpoint, save_checkpoint
 from fmda_amd.ops.gru_ref import bigru_forward, pooled_head
 
-REF_CKPT = "/root/reference/model_params.pt"
+REF_CKPT = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                        "golden", "reference_model_params.pt")
 
 
 def test_checkpoint_roundtrip_with_reference_artifact(tmp_path):
