@@ -51,11 +51,13 @@ extern "C" int fmda_pool_bwd_launch(int is_bf16, const float* dmax,
                                     void* dout, int B, int Tseq, int H,
                                     int n_dir, hipStream_t stream);
 extern "C" int fmda_dropout_launch(int is_bf16, const void* x, void* y,
-                                   long n, float p, unsigned long long seed,
+                                   long n, unsigned int thr, float scale,
+                                   unsigned long long seed,
                                    hipStream_t stream);
 extern "C" int fmda_spatial_dropout_launch(int is_bf16, const void* x,
                                            void* y, long B, long Tlen, long F,
-                                           float p, unsigned long long seed,
+                                           unsigned int thr, float scale,
+                                           unsigned long long seed,
                                            hipStream_t stream);
 extern "C" int fmda_ingest_row_launch(void* ring, const float* row,
                                       const float* xmin, const float* xrng,
@@ -128,6 +130,23 @@ void check_common(const torch::Tensor& gi, const torch::Tensor& w,
                 "hidden size");
 }
 
+// The one place where a dropout probability becomes kernel arguments. Every
+// dropout path (dropout_fused, spatial_dropout_fused and the fused
+// epilogues of gru_fwd / gru_bwd) goes through it, so they agree bitwise.
+//   thr:   8-bit draw threshold, (unsigned)(float(p) * 256.0f)
+//   scale: keep scale 1/(1-p) evaluated in DOUBLE and rounded once to fp32
+//          (torch.nn.functional.dropout's value: p=0.6 -> 2.5 exactly; the
+//          float expression 1.0f/(1.0f-p) gives 2.5000002 there)
+struct DropParams {
+    unsigned int thr;
+    float scale;
+};
+
+DropParams drop_params(double p) {
+    if (!(p > 0.0)) return {0u, 1.0f};
+    return {(unsigned int)((float)p * 256.0f), (float)(1.0 / (1.0 - p))};
+}
+
 }  // namespace
 
 std::vector<torch::Tensor> gru_fwd(torch::Tensor gi, torch::Tensor w,
@@ -152,10 +171,9 @@ std::vector<torch::Tensor> gru_fwd(torch::Tensor gi, torch::Tensor w,
     // fused forward dropout: emit out AND the dropped copy (the layer
     // above's input) from the store epilogue, replacing the separate
     // full-tensor dropout pass. Quantized exactly like dropout_kernel.
-    const unsigned int drop_thr =
-        (drop_p > 0.0) ? (unsigned int)((float)drop_p * 256.0f) : 0u;
-    const float drop_scale =
-        (drop_p > 0.0) ? (float)(1.0 / (1.0 - drop_p)) : 1.0f;
+    const DropParams dp = drop_params(drop_p);
+    const unsigned int drop_thr = dp.thr;
+    const float drop_scale = dp.scale;
     torch::Tensor out_drop;
     void* out_drop_ptr = nullptr;
     if (drop_thr != 0u) {
@@ -260,11 +278,15 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
     }
     auto stream = at::hip::getCurrentHIPStream();
     int rc;
+    // fused inter-layer dropout backward (d_out is w.r.t. the DROPPED
+    // activations; the kernels recompute the counter-based mask at the
+    // dout read instead of a separate full-tensor pass). drop_params()
+    // quantizes EXACTLY like the forward paths, so the recomputed backward
+    // mask can never disagree with the forward one at a rounding boundary.
+    const DropParams dp = drop_params(drop_p);
     if (column_split) {
-        const unsigned int cs_thr =
-            (drop_p > 0.0) ? (unsigned int)((float)drop_p * 256.0f) : 0u;
-        const float cs_scale =
-            (drop_p > 0.0) ? (float)(1.0 / (1.0 - drop_p)) : 1.0f;
+        const unsigned int cs_thr = dp.thr;
+        const float cs_scale = dp.scale;
         const int BR = 256;
         const int GB = (B + BR - 1) / BR;
         const int G = GB * n_dir;
@@ -278,16 +300,8 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
             (unsigned int*)cnt.data_ptr(), B, T, n_dir, cs_thr, cs_scale,
             (unsigned long long)drop_seed, stream.stream());
     } else {
-        // fused inter-layer dropout backward (d_out is w.r.t. the DROPPED
-        // activations; the kernel recomputes the counter-based mask at the
-        // dout read instead of a separate full-tensor pass)
-        // quantized EXACTLY like dropout_kernel's forward threshold
-        // ((unsigned)(float_p * 256.0f)) so the recomputed backward mask
-        // can never disagree with the forward one at a rounding boundary
-        const unsigned int drop_thr =
-            (drop_p > 0.0) ? (unsigned int)((float)drop_p * 256.0f) : 0u;
-        const float drop_scale =
-            (drop_p > 0.0) ? (float)(1.0 / (1.0 - drop_p)) : 1.0f;
+        const unsigned int drop_thr = dp.thr;
+        const float drop_scale = dp.scale;
         TORCH_CHECK(drop_thr == 0u || (is_bf16 && Hp == 128),
                     "fused dropout-backward on this path requires bf16 "
                     "Hp=128");
@@ -443,8 +457,9 @@ torch::Tensor dropout_fused(torch::Tensor x, double p, int64_t seed) {
                 x.scalar_type() == torch::kBFloat16);
     auto y = torch::empty_like(x);
     auto stream = at::hip::getCurrentHIPStream();
+    const DropParams dp = drop_params(p);
     int rc = fmda_dropout_launch(1, x.data_ptr(), y.data_ptr(), x.numel(),
-                                 (float)p, (unsigned long long)seed,
+                                 dp.thr, dp.scale, (unsigned long long)seed,
                                  stream.stream());
     TORCH_CHECK(rc == 0, "dropout launch failed");
     return y;
@@ -456,9 +471,10 @@ torch::Tensor spatial_dropout_fused(torch::Tensor x, double p,
                 x.scalar_type() == torch::kBFloat16);
     auto y = torch::empty_like(x);
     auto stream = at::hip::getCurrentHIPStream();
+    const DropParams dp = drop_params(p);
     int rc = fmda_spatial_dropout_launch(
         1, x.data_ptr(), y.data_ptr(), x.size(0), x.size(1), x.size(2),
-        (float)p, (unsigned long long)seed, stream.stream());
+        dp.thr, dp.scale, (unsigned long long)seed, stream.stream());
     TORCH_CHECK(rc == 0, "spatial dropout launch failed");
     return y;
 }

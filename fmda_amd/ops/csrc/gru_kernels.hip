@@ -426,9 +426,15 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int row = 16 * m + 4 * (lane >> 4) + e;
+                            // explicit fma: left to the compiler, some
+                            // of the unrolled (m, e) chains got fused
+                            // multiply-adds and others a separate multiply
+                            // and add, so a row's rounding depended on its
+                            // slot in the batch tile
                             float s = acc[i][g][m][e];
                             for (int k = 0; k < Hp; ++k)
-                                s += hf_s[row * HFP + k] * wrow[k];
+                                s = __builtin_fmaf(hf_s[row * HFP + k],
+                                                   wrow[k], s);
                             acc[i][g][m][e] = s;
                         }
                 }
@@ -682,9 +688,12 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int row = 16 * m + 4 * (lane >> 4) + e;
+                            // explicit fma, as in the forward kernel: the
+                            // same rounding for every (m, e) row slot
                             float s = acc[g][m][e];
                             for (int k = 0; k < Hp; ++k)
-                                s += to_f32<T>(hb_s[row * WP + k]) * wrow[k];
+                                s = __builtin_fmaf(
+                                    to_f32<T>(hb_s[row * WP + k]), wrow[k], s);
                             acc[g][m][e] = s;
                         }
                 }
@@ -772,8 +781,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                         const int row = 16 * m + 4 * (lane >> 4) + e;
                         float s = acc2[m][e];
                         for (int n = 0; n < 3 * Hp; ++n)
-                            s += to_f32<T>(dgh_s[row * GP3 + n]) *
-                                 ((const float*)wdyn)[(long)n * wstride + jcol];
+                            s = __builtin_fmaf(
+                                to_f32<T>(dgh_s[row * GP3 + n]),
+                                ((const float*)wdyn)[(long)n * wstride + jcol],
+                                s);
                         acc2[m][e] = s;
                     }
             }
@@ -2533,7 +2544,7 @@ void gru_bwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
 
 template <typename T>
 __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y,
-                               long n, float p, float scale,
+                               long n, unsigned int thr, float scale,
                                unsigned long long seed) {
     // 8 elements per thread; the mask bits come from one mix64 per octet
     const long o = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
@@ -2542,7 +2553,6 @@ __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y,
     // 8-bit threshold (p quantized to 1/256 — immaterial for dropout and
     // 9x less hashing, which made the kernel compute-bound).
     const unsigned long long r = mix64(seed ^ (unsigned long long)(o >> 3));
-    const unsigned int thr = (unsigned int)(p * 256.0f);
     if (o + 8 <= n) {
         T v[8];
         *(chunk16*)v = *(const chunk16*)(x + o);  // bf16 x8 = 16 B
@@ -2563,15 +2573,19 @@ __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y,
     }
 }
 
+// (thr, scale) come from the binding's single drop_params(): the fused
+// recurrence epilogues use the very same pair, so all four dropout paths
+// agree bitwise.
 extern "C" int fmda_dropout_launch(int is_bf16, const void* x, void* y,
-                                   long n, float p, unsigned long long seed,
+                                   long n, unsigned int thr, float scale,
+                                   unsigned long long seed,
                                    hipStream_t stream) {
-    const float scale = 1.0f / (1.0f - p);
     const long threads = (n + 7) / 8;
     const dim3 grid((threads + 255) / 256);
     if (is_bf16)
         dropout_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
-            (const __hip_bfloat16*)x, (__hip_bfloat16*)y, n, p, scale, seed);
+            (const __hip_bfloat16*)x, (__hip_bfloat16*)y, n, thr, scale,
+            seed);
     else
         return -2;  // bf16-only: the fp32 paths use torch's dropout
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -2615,11 +2629,10 @@ __global__ void spatial_dropout_kernel(const T* __restrict__ x,
 
 extern "C" int fmda_spatial_dropout_launch(int is_bf16, const void* x,
                                            void* y, long B, long Tlen, long F,
-                                           float p, unsigned long long seed,
+                                           unsigned int thr, float scale,
+                                           unsigned long long seed,
                                            hipStream_t stream) {
     if (!is_bf16) return -2;
-    const float scale = 1.0f / (1.0f - p);
-    const unsigned int thr = (unsigned int)(p * 256.0f);
     const long n = B * Tlen * F;
     const long threads = (n + 7) / 8;
     const dim3 grid((threads + 255) / 256);

@@ -406,15 +406,11 @@ def test_unidirectional_model_on_gpu():
     assert torch.allclose(got, ref, atol=5e-3), (got - ref).abs().max()
 
 
-@pytest.mark.parametrize("B,T,F,H", [(48, 24, 64, 128), (16, 8, 64, 512)])
-def test_deferred_dropout_backward_matches_explicit(B, T, F, H):
-    """The dropout mask applied inside gru_bwd's d_out read (deferred
-    path) must produce the same layer gradients as the explicit
-    _FusedDropout backward pass (same seed, same counter-based mask) —
-    on the v3 (H=128) and column-split (H=512) kernels."""
+def _deferred_vs_explicit_dropout(B, T, F, H, p_drop):
     from fmda_amd.ops.interface import _BiGRULayer, _FusedDropout
+    import oracles as orc
     torch.manual_seed(3)
-    p_drop, seed = 0.3, 987654321
+    seed = 987654321
     masters = []
     for _ in range(2):
         masters += [torch.randn(3 * H, F, device="cuda") * 0.2,
@@ -437,15 +433,39 @@ def test_deferred_dropout_backward_matches_explicit(B, T, F, H):
             dropped = _FusedDropout.apply(out, p_drop, seed)
         ((dropped.float() * gup.float()).sum()
          + (hl * ghl).sum()).backward()
-        return [m.grad.clone() for m in ms], dropped.detach()
+        return [m.grad.clone() for m in ms], dropped.detach(), out.detach()
 
-    ga, da = run(True)
-    gb, db = run(False)
+    ga, da, oa = run(True)
+    gb, db, ob = run(False)
+    assert torch.equal(oa, ob)
     assert torch.equal(da, db)  # forward mask identical by construction
+    # ... and both are the host counter-hash oracle applied to `out`
+    assert torch.equal(da.cpu(), orc.dropout_ref(oa, p_drop, seed))
     tol = 2e-2 if H <= 128 else 8e-2   # bf16 compounding at H=512
     for i, (a, b) in enumerate(zip(ga, gb)):
         rel = (a - b).norm() / b.norm().clamp(min=1e-12)
         assert rel < tol, (i, float(rel))
+
+
+# B=37 is a partial tile for both the 16-row forward and the 32-row
+# backward tiling of the H=128 kernels
+@pytest.mark.parametrize("B,T,F,H", [(48, 24, 64, 128), (16, 8, 64, 512),
+                                     (37, 24, 64, 128)])
+def test_deferred_dropout_backward_matches_explicit(B, T, F, H):
+    """The dropout mask applied inside gru_bwd's d_out read (deferred
+    path) must produce the same layer gradients as the explicit
+    _FusedDropout backward pass (same seed, same counter-based mask) —
+    on the v3 (H=128) and column-split (H=512) kernels."""
+    _deferred_vs_explicit_dropout(B, T, F, H, 0.3)
+
+
+@pytest.mark.parametrize("B,T,F,H", [(48, 24, 64, 128), (16, 8, 64, 512),
+                                     (37, 24, 64, 128)])
+def test_deferred_dropout_backward_matches_explicit_p06(B, T, F, H):
+    """Same at p=0.6, where 1/(1-p) evaluated in float (2.5000002) and in
+    double (2.5) differ: the fused epilogue and dropout_kernel must use the
+    same keep scale."""
+    _deferred_vs_explicit_dropout(B, T, F, H, 0.6)
 
 
 def test_padded_hidden_h8_model_matches_cpu():
