@@ -64,15 +64,25 @@ def chunked_outer(dg: torch.Tensor, x: torch.Tensor,
     MI355X for the training-step dW shapes. out_fp32=True returns the fp32
     chunk sum directly — callers that want fp32 master-grads then skip a
     round trip through the compute dtype (two elementwise kernels each)."""
+    parts = chunked_outer_parts(dg, x, chunks)
+    if parts.shape[0] == 1:
+        return parts[0].float() if out_fp32 else parts[0]
+    s = parts.float().sum(dim=0)
+    return s if out_fp32 else s.to(dg.dtype)
+
+
+def chunked_outer_parts(dg: torch.Tensor, x: torch.Tensor,
+                        chunks: int = 64) -> torch.Tensor:
+    """The raw split-K partials of `chunked_outer`: (c, N, K) in the input
+    dtype, whose sum over c is (M, N)^T @ (M, K). c is the largest halving
+    of `chunks` that divides M; with no even split it is 1 (one plain
+    GEMM). For callers that reduce the partials themselves."""
     M, N = dg.shape
     K = x.shape[1]
     c = chunks
     while c > 1 and M % c != 0:
         c //= 2
     if c <= 1:
-        r = torch.matmul(dg.t(), x)
-        return r.float() if out_fp32 else r
-    parts = torch.bmm(dg.view(c, M // c, N).transpose(1, 2),
-                      x.view(c, M // c, K))
-    s = parts.float().sum(dim=0)
-    return s if out_fp32 else s.to(dg.dtype)
+        return torch.matmul(dg.t(), x).unsqueeze(0)
+    return torch.bmm(dg.view(c, M // c, N).transpose(1, 2),
+                     x.view(c, M // c, K))

@@ -43,13 +43,15 @@ extern "C" int fmda_gru_bwd_launch(int is_bf16, int Hp, const void* gi,
                                    hipStream_t stream);
 extern "C" int fmda_mfma_selftest_launch(const void* A, const void* Bm,
                                          float* C, hipStream_t stream);
-extern "C" int fmda_pool_fwd_launch(int is_bf16, const void* out, float* maxv,
-                                    float* avgv, int* amax, int B, int Tseq,
-                                    int H, int n_dir, hipStream_t stream);
-extern "C" int fmda_pool_bwd_launch(int is_bf16, const float* dmax,
-                                    const float* davg, const int* amax,
+extern "C" int fmda_pool_fwd_launch(int is_bf16, const void* out, void* maxv,
+                                    void* avgv, int* amax, int B, int Tseq,
+                                    int H, int n_dir, int act_io,
+                                    hipStream_t stream);
+extern "C" int fmda_pool_bwd_launch(int is_bf16, const void* dmax,
+                                    const void* davg, const int* amax,
                                     void* dout, int B, int Tseq, int H,
-                                    int n_dir, hipStream_t stream);
+                                    int n_dir, int act_io, long ld_max,
+                                    long ld_avg, hipStream_t stream);
 extern "C" int fmda_dropout_launch(int is_bf16, const void* x, void* y,
                                    long n, unsigned int thr, float scale,
                                    unsigned long long seed,
@@ -88,6 +90,29 @@ extern "C" int fmda_gru_db_reduce_launch(const float* part, int rows,
                                          float* dbih, hipStream_t stream);
 extern "C" int fmda_opt_norm2_launch(const void* chunks, int n_chunks,
                                      float* out, hipStream_t stream);
+// glue_kernels.hip
+extern "C" int fmda_pack_gru_layer_launch(
+        int is_bf16, const float* const* masters, void* w_ih_cat,
+        void* b_ih_cat, void* w_hh_cat, float* b_hh_cat, void* wt, int D,
+        int H, int Hp, int F, hipStream_t stream);
+extern "C" int fmda_finalize_gru_wgrads_launch(
+        int part_bf16, const void* part_ih, int c_ih, const void* part_hh,
+        int c_hh, float* const* grads, int D, int H, int Hp, int F,
+        hipStream_t stream);
+extern "C" int fmda_head_fwd_master_launch(
+        int is_bf16, const void* x, const float* W, const float* bias,
+        const float* y, const float* wgt, const float* pw, float* logits,
+        float* sig, float* loss_sum, int B, int K, int C,
+        hipStream_t stream);
+extern "C" int fmda_head_bwd_master_launch(
+        int is_bf16, const float* sig, const float* y, const float* wgt,
+        const float* pw, const float* gscale, const float* W,
+        float* dlogits, void* dx, int B, int K, int C, hipStream_t stream);
+extern "C" int fmda_head_wgrads_slabs(int B);
+extern "C" int fmda_head_wgrads_launch(
+        int is_bf16, const float* dlogits, const void* x, float* dw_part,
+        float* db_part, float* dW, float* db, int B, int K, int C,
+        hipStream_t stream);
 namespace fmda_ckpt {
 void save_state_dict(const std::string& path,
                      const std::vector<std::string>& keys,
@@ -222,7 +247,8 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
                                    torch::Tensor bhh, torch::Tensor out,
                                    torch::Tensor dout, torch::Tensor dhT,
                                    double drop_p, int64_t drop_seed,
-                                   c10::optional<torch::Tensor> h0_opt) {
+                                   c10::optional<torch::Tensor> h0_opt,
+                                   c10::optional<torch::Tensor> wt_opt) {
     int B, T, n_dir, Hp;
     bool is_bf16;
     check_common(gi, w, bhh, B, T, n_dir, Hp, is_bf16);
@@ -269,11 +295,21 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
     auto dbpart = torch::zeros({db_rows, n_dir, 4 * Hp},
                                gi.options().dtype(torch::kFloat32));
     // W^T for the carry GEMM's B fragments (v3 kernel streams them from
-    // L2 as contiguous bf16x8 rows instead of hoisting 48 VGPRs).
+    // L2 as contiguous bf16x8 rows instead of hoisting 48 VGPRs). A caller
+    // that packed the weights with pack_gru_layer already has it.
     torch::Tensor wt;
     const void* wt_ptr = nullptr;
     if (is_bf16 && (Hp == 128 || Hp == 512)) {
-        wt = w.transpose(1, 2).contiguous();
+        if (wt_opt.has_value()) {
+            wt = wt_opt.value();
+            TORCH_CHECK(wt.is_cuda() && wt.is_contiguous() &&
+                        wt.scalar_type() == w.scalar_type() &&
+                        wt.sizes() == torch::IntArrayRef(
+                            {n_dir, Hp, (int64_t)3 * Hp}),
+                        "wt must be contiguous (n_dir, Hp, 3Hp) in w's dtype");
+        } else {
+            wt = w.transpose(1, 2).contiguous();
+        }
         wt_ptr = wt.data_ptr();
     }
     auto stream = at::hip::getCurrentHIPStream();
@@ -343,7 +379,10 @@ torch::Tensor mfma_selftest(torch::Tensor A, torch::Tensor Bm) {
     return C;
 }
 
-std::vector<torch::Tensor> pool_fwd(torch::Tensor out, int64_t n_dir) {
+// act_dtype: return max / avg in out's dtype instead of fp32 (the kernel
+// rounds where the caller's .to(out.dtype) would have).
+std::vector<torch::Tensor> pool_fwd(torch::Tensor out, int64_t n_dir,
+                                    bool act_dtype) {
     TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 3);
     const bool bf16 = out.scalar_type() == torch::kBFloat16;
     TORCH_CHECK(bf16 || out.scalar_type() == torch::kFloat32);
@@ -351,15 +390,17 @@ std::vector<torch::Tensor> pool_fwd(torch::Tensor out, int64_t n_dir) {
     const int H = out.size(2) / n_dir;
     TORCH_CHECK(H % 2 == 0, "pool_fwd pairs columns: H must be even "
                 "(odd H uses the eager path)");
-    auto f32 = out.options().dtype(torch::kFloat32);
-    auto maxv = torch::empty({B, H}, f32);
-    auto avgv = torch::empty({B, H}, f32);
+    const bool act_io = act_dtype && bf16;   // fp32 activations: same thing
+    auto pooled = out.options().dtype(act_io ? torch::kBFloat16
+                                             : torch::kFloat32);
+    auto maxv = torch::empty({B, H}, pooled);
+    auto avgv = torch::empty({B, H}, pooled);
     auto amax = torch::empty({B, H}, out.options().dtype(torch::kInt32));
     auto stream = at::hip::getCurrentHIPStream();
     int rc = fmda_pool_fwd_launch(bf16 ? 1 : 0, out.data_ptr(),
-                                  maxv.data_ptr<float>(), avgv.data_ptr<float>(),
+                                  maxv.data_ptr(), avgv.data_ptr(),
                                   amax.data_ptr<int>(), B, T, H, (int)n_dir,
-                                  stream.stream());
+                                  act_io ? 1 : 0, stream.stream());
     TORCH_CHECK(rc == 0, "pool_fwd launch failed");
     return {maxv, avgv, amax};
 }
@@ -367,14 +408,29 @@ std::vector<torch::Tensor> pool_fwd(torch::Tensor out, int64_t n_dir) {
 torch::Tensor pool_bwd(torch::Tensor dmax, torch::Tensor davg,
                        torch::Tensor amax, int64_t T, int64_t n_dir,
                        torch::ScalarType dtype) {
-    TORCH_CHECK(dmax.is_cuda() && dmax.is_contiguous() && davg.is_contiguous());
+    // rows may be pitched (column slices of the pooled-feature gradient)
+    TORCH_CHECK(dmax.is_cuda() && davg.is_cuda() && dmax.dim() == 2 &&
+                davg.sizes() == dmax.sizes() && amax.sizes() == dmax.sizes() &&
+                amax.is_contiguous(), "pool_bwd: shape mismatch");
     const int B = dmax.size(0), H = dmax.size(1);
+    TORCH_CHECK((H == 1 || (dmax.stride(1) == 1 && davg.stride(1) == 1)) &&
+                (B == 1 || (dmax.stride(0) >= H && davg.stride(0) >= H)),
+                "pool_bwd: dmax / davg need unit column stride");
     const bool bf16 = dtype == torch::kBFloat16;
+    // dmax / davg come in fp32, or for bf16 activations in bf16 as well
+    const bool act_io = bf16 && dmax.scalar_type() == torch::kBFloat16;
+    TORCH_CHECK(dmax.scalar_type() == davg.scalar_type() &&
+                (act_io || dmax.scalar_type() == torch::kFloat32),
+                "pool_bwd: dmax / davg must both be fp32, or both bf16 with "
+                "bf16 activations");
     auto dout = torch::empty({B, T, n_dir * H}, dmax.options().dtype(dtype));
     auto stream = at::hip::getCurrentHIPStream();
-    int rc = fmda_pool_bwd_launch(bf16 ? 1 : 0, dmax.data_ptr<float>(),
-                                  davg.data_ptr<float>(), amax.data_ptr<int>(),
+    int rc = fmda_pool_bwd_launch(bf16 ? 1 : 0, dmax.data_ptr(),
+                                  davg.data_ptr(), amax.data_ptr<int>(),
                                   dout.data_ptr(), B, (int)T, H, (int)n_dir,
+                                  act_io ? 1 : 0,
+                                  B == 1 ? H : (long)dmax.stride(0),
+                                  B == 1 ? H : (long)davg.stride(0),
                                   stream.stream());
     TORCH_CHECK(rc == 0, "pool_bwd launch failed");
     return dout;
@@ -537,6 +593,182 @@ torch::Tensor head_sigmoid(torch::Tensor x, torch::Tensor W,
     return probs;
 }
 
+namespace {
+
+void check_f32_cuda(const torch::Tensor& t, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                t.scalar_type() == torch::kFloat32,
+                what, " must be a contiguous fp32 GPU tensor");
+}
+
+bool compute_dtype_is_bf16(torch::ScalarType dtype) {
+    TORCH_CHECK(dtype == torch::kBFloat16 || dtype == torch::kFloat32,
+                "compute dtype must be bf16 or fp32");
+    return dtype == torch::kBFloat16;
+}
+
+}  // namespace
+
+// masters: [w_ih (3H,F), w_hh (3H,H), b_ih (3H), b_hh (3H)] per direction,
+// fp32. Returns {w_ih_cat (D*3Hp,F), b_ih_cat (D*3Hp), w_hh_cat (D,3Hp,Hp),
+// b_hh_cat (D,3Hp) fp32, wt (D,Hp,3Hp)}: gate rows zero-padded H -> Hp, the
+// first three and wt in `dtype`.
+std::vector<torch::Tensor> pack_gru_layer(std::vector<torch::Tensor> masters,
+                                          int64_t Hp,
+                                          torch::ScalarType dtype) {
+    TORCH_CHECK(masters.size() == 4 || masters.size() == 8,
+                "pack_gru_layer: 4 masters per direction, 1 or 2 directions");
+    const int64_t D = masters.size() / 4;
+    for (auto& t : masters) check_f32_cuda(t, "pack_gru_layer: master");
+    TORCH_CHECK(masters[0].dim() == 2 && masters[1].dim() == 2,
+                "pack_gru_layer: bad weight ranks");
+    const int64_t H = masters[1].size(1), F = masters[0].size(1);
+    TORCH_CHECK(H <= Hp, "pack_gru_layer: H > Hp");
+    const float* ptrs[8] = {};
+    for (int64_t d = 0; d < D; ++d) {
+        TORCH_CHECK(masters[4 * d].sizes() == torch::IntArrayRef({3 * H, F}) &&
+                    masters[4 * d + 1].sizes() ==
+                        torch::IntArrayRef({3 * H, H}) &&
+                    masters[4 * d + 2].sizes() == torch::IntArrayRef({3 * H}) &&
+                    masters[4 * d + 3].sizes() == torch::IntArrayRef({3 * H}),
+                    "pack_gru_layer: master shapes disagree");
+        for (int k = 0; k < 4; ++k)
+            ptrs[4 * d + k] = masters[4 * d + k].data_ptr<float>();
+    }
+    const bool bf16 = compute_dtype_is_bf16(dtype);
+    auto opt = masters[0].options().dtype(dtype);
+    auto w_ih_cat = torch::empty({D * 3 * Hp, F}, opt);
+    auto b_ih_cat = torch::empty({D * 3 * Hp}, opt);
+    auto w_hh_cat = torch::empty({D, 3 * Hp, Hp}, opt);
+    auto b_hh_cat = torch::empty({D, 3 * Hp}, masters[0].options());
+    auto wt = torch::empty({D, Hp, 3 * Hp}, opt);
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_pack_gru_layer_launch(
+        bf16 ? 1 : 0, ptrs, w_ih_cat.data_ptr(), b_ih_cat.data_ptr(),
+        w_hh_cat.data_ptr(), b_hh_cat.data_ptr<float>(), wt.data_ptr(),
+        (int)D, (int)H, (int)Hp, (int)F, stream.stream());
+    TORCH_CHECK(rc == 0, "pack_gru_layer launch failed");
+    return {w_ih_cat, b_ih_cat, w_hh_cat, b_hh_cat, wt};
+}
+
+// part_ih: (c, D*3Hp, F) split-K partials of dGi^T x; part_hh:
+// (c, D*3Hp, D*Hp) partials of dGh^T out. Returns the fp32 master-shaped
+// {dW_ih[0] (3H,F), dW_hh[0] (3H,H), dW_ih[1], dW_hh[1]}.
+std::vector<torch::Tensor> finalize_gru_wgrads(torch::Tensor part_ih,
+                                               torch::Tensor part_hh,
+                                               int64_t D, int64_t H,
+                                               int64_t Hp) {
+    TORCH_CHECK(part_ih.is_cuda() && part_hh.is_cuda() &&
+                part_ih.is_contiguous() && part_hh.is_contiguous() &&
+                part_ih.dim() == 3 && part_hh.dim() == 3,
+                "finalize_gru_wgrads: partials must be contiguous (c, N, K) "
+                "GPU tensors");
+    TORCH_CHECK(part_ih.scalar_type() == part_hh.scalar_type(),
+                "finalize_gru_wgrads: partial dtypes disagree");
+    const bool bf16 = compute_dtype_is_bf16(part_ih.scalar_type());
+    TORCH_CHECK((D == 1 || D == 2) && H >= 1 && H <= Hp,
+                "finalize_gru_wgrads: bad D / H / Hp");
+    const int64_t F = part_ih.size(2);
+    TORCH_CHECK(part_ih.size(1) == D * 3 * Hp &&
+                part_hh.size(1) == D * 3 * Hp && part_hh.size(2) == D * Hp,
+                "finalize_gru_wgrads: partial shapes disagree with D / Hp");
+    auto f32 = part_ih.options().dtype(torch::kFloat32);
+    std::vector<torch::Tensor> grads;
+    float* ptrs[4] = {};
+    for (int64_t d = 0; d < D; ++d) {
+        grads.push_back(torch::empty({3 * H, F}, f32));
+        grads.push_back(torch::empty({3 * H, H}, f32));
+        ptrs[2 * d] = grads[2 * d].data_ptr<float>();
+        ptrs[2 * d + 1] = grads[2 * d + 1].data_ptr<float>();
+    }
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_finalize_gru_wgrads_launch(
+        bf16 ? 1 : 0, part_ih.data_ptr(), (int)part_ih.size(0),
+        part_hh.data_ptr(), (int)part_hh.size(0), ptrs, (int)D, (int)H,
+        (int)Hp, (int)F, stream.stream());
+    TORCH_CHECK(rc == 0, "finalize_gru_wgrads launch failed");
+    return grads;
+}
+
+// head_loss_fwd on the fp32 master W (C, K) and b (C): each value is rounded
+// to x's dtype in registers, so the results equal head_loss_fwd on W.to(x),
+// b.to(x) bit for bit.
+std::vector<torch::Tensor> head_loss_fwd_master(
+        torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor y,
+        torch::Tensor wgt, torch::Tensor pw) {
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2);
+    const bool bf16 = compute_dtype_is_bf16(x.scalar_type());
+    check_f32_cuda(W, "head W"); check_f32_cuda(b, "head b");
+    check_f32_cuda(y, "head y"); check_f32_cuda(wgt, "head weight");
+    check_f32_cuda(pw, "head pos_weight");
+    const int B = x.size(0), K = x.size(1), C = W.size(0);
+    TORCH_CHECK(W.size(1) == K && b.numel() == C && y.numel() == (int64_t)B * C
+                && wgt.numel() == C && pw.numel() == C,
+                "head_loss_fwd_master: shape mismatch");
+    auto f32 = x.options().dtype(torch::kFloat32);
+    auto logits = torch::empty({B, C}, f32);
+    auto sig = torch::empty({B, C}, f32);
+    auto part = torch::empty({((int64_t)B * C + 255) / 256}, f32);
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_head_fwd_master_launch(
+        bf16 ? 1 : 0, x.data_ptr(), W.data_ptr<float>(), b.data_ptr<float>(),
+        y.data_ptr<float>(), wgt.data_ptr<float>(), pw.data_ptr<float>(),
+        logits.data_ptr<float>(), sig.data_ptr<float>(),
+        part.data_ptr<float>(), B, K, C, stream.stream());
+    TORCH_CHECK(rc == 0, "head fwd (master) launch failed");
+    return {logits, sig, part.sum().reshape({1})};
+}
+
+std::vector<torch::Tensor> head_loss_bwd_master(
+        torch::Tensor sig, torch::Tensor y, torch::Tensor wgt,
+        torch::Tensor pw, torch::Tensor gscale, torch::Tensor W,
+        torch::ScalarType xdtype) {
+    check_f32_cuda(sig, "head sig"); check_f32_cuda(y, "head y");
+    check_f32_cuda(wgt, "head weight"); check_f32_cuda(pw, "head pos_weight");
+    check_f32_cuda(gscale, "head gscale"); check_f32_cuda(W, "head W");
+    const int B = sig.size(0), C = sig.size(1), K = W.size(1);
+    TORCH_CHECK(W.size(0) == C && y.numel() == sig.numel() &&
+                wgt.numel() == C && pw.numel() == C && gscale.numel() == 1,
+                "head_loss_bwd_master: shape mismatch");
+    const bool bf16 = compute_dtype_is_bf16(xdtype);
+    auto dlogits = torch::empty_like(sig);
+    auto dx = torch::empty({B, K}, sig.options().dtype(xdtype));
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_head_bwd_master_launch(
+        bf16 ? 1 : 0, sig.data_ptr<float>(), y.data_ptr<float>(),
+        wgt.data_ptr<float>(), pw.data_ptr<float>(),
+        gscale.data_ptr<float>(), W.data_ptr<float>(),
+        dlogits.data_ptr<float>(), dx.data_ptr(), B, K, C, stream.stream());
+    TORCH_CHECK(rc == 0, "head bwd (master) launch failed");
+    return {dlogits, dx};
+}
+
+// dW (C, K) = round_x(dlogits)^T x and db (C) = sum_rows dlogits, both fp32,
+// reduced over the batch in two fixed-order stages.
+std::vector<torch::Tensor> head_wgrads(torch::Tensor dlogits,
+                                       torch::Tensor x) {
+    check_f32_cuda(dlogits, "head dlogits");
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 &&
+                dlogits.dim() == 2 && dlogits.size(0) == x.size(0),
+                "head_wgrads: shape mismatch");
+    const bool bf16 = compute_dtype_is_bf16(x.scalar_type());
+    const int B = x.size(0), K = x.size(1), C = dlogits.size(1);
+    const int64_t n_slabs = fmda_head_wgrads_slabs(B);
+    auto f32 = dlogits.options();
+    auto dw_part = torch::empty({n_slabs, C, K}, f32);
+    auto db_part = torch::empty({n_slabs, C}, f32);
+    auto dW = torch::empty({C, K}, f32);
+    auto db = torch::empty({C}, f32);
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_head_wgrads_launch(
+        bf16 ? 1 : 0, dlogits.data_ptr<float>(), x.data_ptr(),
+        dw_part.data_ptr<float>(), db_part.data_ptr<float>(),
+        dW.data_ptr<float>(), db.data_ptr<float>(), B, K, C,
+        stream.stream());
+    TORCH_CHECK(rc == 0, "head_wgrads launch failed");
+    return {dW, db};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gru_fwd", &gru_fwd, "fused biGRU recurrence forward (HIP/CDNA4)",
           py::arg("gi"), py::arg("w"), py::arg("bhh"),
@@ -545,7 +777,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gru_bwd", &gru_bwd, "fused biGRU recurrence backward (HIP/CDNA4)",
           py::arg("gi"), py::arg("w"), py::arg("bhh"), py::arg("out"),
           py::arg("dout"), py::arg("dhT"), py::arg("drop_p") = 0.0,
-          py::arg("drop_seed") = 0, py::arg("h0") = py::none());
+          py::arg("drop_seed") = 0, py::arg("h0") = py::none(),
+          py::arg("wt") = py::none());
     m.def("mfma_selftest", &mfma_selftest, "mfma fragment layout self-test");
     m.def("dropout_fused", &dropout_fused,
           "counter-based dropout (mask recomputed in backward)");
@@ -557,10 +790,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused [dirsum(h_last) | max | avg] concat for inference");
     m.def("head_sigmoid", &head_sigmoid,
           "linear head + sigmoid emitting probabilities");
-    m.def("pool_fwd", &pool_fwd, "fused dirsum+max/avg pooling forward");
+    m.def("pool_fwd", &pool_fwd, "fused dirsum+max/avg pooling forward",
+          py::arg("out"), py::arg("n_dir"), py::arg("act_dtype") = false);
     m.def("pool_bwd", &pool_bwd, "fused pooling backward (d_out assembly)");
     m.def("head_loss_fwd", &head_loss_fwd, "fused head GEMM + BCE loss");
     m.def("head_loss_bwd", &head_loss_bwd, "fused head/loss backward");
+    m.def("pack_gru_layer", &pack_gru_layer,
+          "fp32 masters -> padded compute-dtype layer weights (+ W_hh^T)");
+    m.def("finalize_gru_wgrads", &finalize_gru_wgrads,
+          "split-K partials -> master-shaped fp32 dW_ih / dW_hh");
+    m.def("head_loss_fwd_master", &head_loss_fwd_master,
+          "fused head GEMM + BCE loss reading the fp32 master W / b");
+    m.def("head_loss_bwd_master", &head_loss_bwd_master,
+          "fused head/loss backward reading the fp32 master W");
+    m.def("head_wgrads", &head_wgrads,
+          "head dW / db in fp32, two-stage fixed-order batch reduction");
     m.def("fused_clip_adam", &fused_clip_adam,
           "fused multi-tensor grad-clip + Adam step");
     m.def("save_state_dict_native", &fmda_ckpt::save_state_dict,

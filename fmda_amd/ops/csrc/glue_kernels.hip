@@ -1,0 +1,424 @@
+// fmda_amd glue kernels for MI355X (gfx950): the small per-step passes
+// around the recurrence and the library GEMMs, each done in one launch.
+//
+// A training step re-derives everything below from the fp32 master weights
+// (Adam moves them every step), so none of it can be cached:
+//   pack_gru_layer       masters -> padded, direction-stacked compute-dtype
+//                        weights (+ W_hh^T for the BPTT carry GEMM)
+//   finalize_gru_wgrads  split-K GEMM partials -> the four master-shaped
+//                        fp32 weight gradients of a layer
+//   head_*_master        classifier head + loss reading the fp32 masters
+//   head_wgrads          dW / db of the head, two-stage over the batch
+// All sums run in a fixed order: results are bitwise reproducible.
+#include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+
+#define FMDA_DEV __device__ __forceinline__
+
+namespace fmda {
+namespace {
+
+#define FMDA_LOG2E 1.4426950408889634f
+
+FMDA_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+FMDA_DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+// same formula as the head kernels in gru_kernels.hip (bit-identical sig)
+FMDA_DEV float sigmoidf(float x) {
+    return fast_rcp(1.0f + fast_exp2(-x * FMDA_LOG2E));
+}
+
+template <typename T> FMDA_DEV float to_f32(T v);
+template <> FMDA_DEV float to_f32<float>(float v) { return v; }
+template <> FMDA_DEV float to_f32<__hip_bfloat16>(__hip_bfloat16 v) {
+    return __bfloat162float(v);
+}
+template <typename T> FMDA_DEV T from_f32(float v);
+template <> FMDA_DEV float from_f32<float>(float v) { return v; }
+template <> FMDA_DEV __hip_bfloat16 from_f32<__hip_bfloat16>(float v) {
+    return __float2bfloat16(v);   // round to nearest even, like .to(bf16)
+}
+// fp32 master value as the compute dtype sees it
+template <typename T> FMDA_DEV float round_to(float v) {
+    return to_f32<T>(from_f32<T>(v));
+}
+
+// ===========================================================================
+// pack_gru_layer
+// ===========================================================================
+struct GruMasters {
+    const float* w_ih[2];   // (3H, F)
+    const float* w_hh[2];   // (3H, H)
+    const float* b_ih[2];   // (3H)
+    const float* b_hh[2];   // (3H)
+};
+
+// One flat index space over the five outputs, walked grid-stride. Padded
+// gate row g*Hp + j reads master row g*H + j; rows j >= H and recurrent
+// columns >= H are zero.
+template <typename T>
+__global__ void pack_gru_layer_kernel(GruMasters m, T* __restrict__ w_ih_cat,
+                                      T* __restrict__ b_ih_cat,
+                                      T* __restrict__ w_hh_cat,
+                                      float* __restrict__ b_hh_cat,
+                                      T* __restrict__ wt, int D, int H,
+                                      int Hp, int F) {
+    const long G3 = 3L * Hp;
+    const long n_ih = (long)D * G3 * F;
+    const long n_hh = (long)D * G3 * Hp;
+    const long n_b = (long)D * G3;
+    const long total = n_ih + 2 * n_hh + 2 * n_b;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += stride) {
+        if (i < n_ih) {
+            const int d = (int)(i / (G3 * F));
+            const long rem = i % (G3 * F);
+            const int row = (int)(rem / F), col = (int)(rem % F);
+            const int g = row / Hp, j = row % Hp;
+            const float v =
+                j < H ? m.w_ih[d][((long)g * H + j) * F + col] : 0.0f;
+            w_ih_cat[i] = from_f32<T>(v);
+        } else if (i < n_ih + n_hh) {
+            const long o = i - n_ih;
+            const int d = (int)(o / (G3 * Hp));
+            const long rem = o % (G3 * Hp);
+            const int row = (int)(rem / Hp), col = (int)(rem % Hp);
+            const int g = row / Hp, j = row % Hp;
+            const float v = (j < H && col < H)
+                ? m.w_hh[d][((long)g * H + j) * H + col] : 0.0f;
+            w_hh_cat[o] = from_f32<T>(v);
+        } else if (i < n_ih + 2 * n_hh) {
+            // wt[d][k][n] = w_hh_cat[d][n][k]
+            const long o = i - n_ih - n_hh;
+            const int d = (int)(o / (G3 * Hp));
+            const long rem = o % (G3 * Hp);
+            const int k = (int)(rem / G3), n = (int)(rem % G3);
+            const int g = n / Hp, j = n % Hp;
+            const float v = (j < H && k < H)
+                ? m.w_hh[d][((long)g * H + j) * H + k] : 0.0f;
+            wt[o] = from_f32<T>(v);
+        } else {
+            long o = i - n_ih - 2 * n_hh;
+            const bool hh = o >= n_b;
+            if (hh) o -= n_b;
+            const int d = (int)(o / G3);
+            const int row = (int)(o % G3);
+            const int g = row / Hp, j = row % Hp;
+            const float* src = hh ? m.b_hh[d] : m.b_ih[d];
+            const float v = j < H ? src[g * H + j] : 0.0f;
+            if (hh) b_hh_cat[o] = v;
+            else b_ih_cat[o] = from_f32<T>(v);
+        }
+    }
+}
+
+// ===========================================================================
+// finalize_gru_wgrads
+// ===========================================================================
+struct GruWgrads {
+    float* dw_ih[2];   // (3H, F)
+    float* dw_hh[2];   // (3H, H)
+};
+
+// One thread per output element. part_ih: (c_ih, D*3Hp, F) partials of
+// dGi^T x; part_hh: (c_hh, D*3Hp, D*Hp) partials of dGh^T out, of which
+// only the diagonal direction blocks are read. Chunks are summed in fp32 in
+// ascending order; gate rows (and dW_hh columns) are unpadded on the way.
+template <typename PT>
+__global__ void finalize_gru_wgrads_kernel(const PT* __restrict__ part_ih,
+                                           int c_ih,
+                                           const PT* __restrict__ part_hh,
+                                           int c_hh, GruWgrads o, int D,
+                                           int H, int Hp, int F) {
+    const long n_ih = 3L * H * F;
+    const long n_hh = 3L * H * H;
+    const long per_dir = n_ih + n_hh;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)D * per_dir) return;
+    const int d = (int)(idx / per_dir);
+    const long r = idx % per_dir;
+    float acc = 0.0f;
+    if (r < n_ih) {
+        const int row = (int)(r / F), col = (int)(r % F);
+        const long prow = (long)d * 3 * Hp + (long)(row / H) * Hp + row % H;
+        const PT* p = part_ih + prow * F + col;
+        const long cs = (long)D * 3 * Hp * F;
+#pragma unroll 8
+        for (int k = 0; k < c_ih; ++k) acc += to_f32<PT>(p[k * cs]);
+        o.dw_ih[d][r] = acc;
+    } else {
+        const long q = r - n_ih;
+        const int row = (int)(q / H), col = (int)(q % H);
+        const long prow = (long)d * 3 * Hp + (long)(row / H) * Hp + row % H;
+        const long pitch = (long)D * Hp;
+        const PT* p = part_hh + prow * pitch + (long)d * Hp + col;
+        const long cs = (long)D * 3 * Hp * pitch;
+#pragma unroll 8
+        for (int k = 0; k < c_hh; ++k) acc += to_f32<PT>(p[k * cs]);
+        o.dw_hh[d][q] = acc;
+    }
+}
+
+// ===========================================================================
+// Classifier head + BCEWithLogitsLoss(weight, pos_weight) on the fp32
+// master W / b. The arithmetic is head_loss_{fwd,bwd}_kernel's
+// (gru_kernels.hip) with each master value rounded to the compute dtype T
+// in registers, so logits, sig, loss and dx are bit-identical to casting W
+// and b first.
+// ===========================================================================
+template <typename T>
+__global__ void head_fwd_master_kernel(const T* __restrict__ x,
+                                       const float* __restrict__ W,
+                                       const float* __restrict__ bias,
+                                       const float* __restrict__ y,
+                                       const float* __restrict__ wgt,
+                                       const float* __restrict__ pw,
+                                       float* __restrict__ logits,
+                                       float* __restrict__ sig,
+                                       float* __restrict__ loss_sum, int B,
+                                       int K, int C) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    float l = 0.0f;
+    if (idx < B * C) {
+        const int r = idx / C, c = idx % C;
+        const T* xr = x + (long)r * K;
+        const float* wr = W + (long)c * K;
+        float acc = round_to<T>(bias[c]);
+        for (int k = 0; k < K; ++k)
+            acc += to_f32<T>(xr[k]) * round_to<T>(wr[k]);
+        logits[idx] = acc;
+        const float s = sigmoidf(acc);
+        sig[idx] = s;
+        const float yy = y[idx];
+        const float m = acc > 0.0f ? acc : 0.0f;
+        const float lse = m + __builtin_logf(fast_exp2(-m * FMDA_LOG2E) +
+                                             fast_exp2((acc - m) * FMDA_LOG2E));
+        const float log_s = acc - lse;
+        const float log_1ms = -lse;
+        l = -wgt[c] * (pw[c] * yy * log_s + (1.0f - yy) * log_1ms);
+    }
+    // one partial per block, summed by the caller in a fixed order
+    __shared__ float red[4];
+    float v = l;
+    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+        loss_sum[blockIdx.x] = t;
+    }
+}
+
+template <typename T>
+__global__ void head_bwd_master_kernel(const float* __restrict__ sig,
+                                       const float* __restrict__ y,
+                                       const float* __restrict__ wgt,
+                                       const float* __restrict__ pw,
+                                       const float* __restrict__ gscale,
+                                       const float* __restrict__ W,
+                                       float* __restrict__ dlogits,
+                                       T* __restrict__ dx, int B, int K,
+                                       int C) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * K) return;
+    const int r = idx / K, k = idx % K;
+    const float g = *gscale / (float)(B * C);
+    float acc = 0.0f;
+    for (int c = 0; c < C; ++c) {
+        const float s = sig[r * C + c];
+        const float yy = y[r * C + c];
+        const float dl = g * wgt[c] * (s * (1.0f - yy + pw[c] * yy) -
+                                       pw[c] * yy);
+        if (k == 0) dlogits[r * C + c] = dl;
+        acc += dl * round_to<T>(W[(long)c * K + k]);
+    }
+    dx[idx] = from_f32<T>(acc);
+}
+
+// ---------------------------------------------------------------------------
+// head_wgrads: dW[c][k] = sum_r round_T(dlogits[r][c]) * x[r][k] and
+// db[c] = sum_r dlogits[r][c], in fp32 and in two stages with a fixed
+// order: stage 1 sums slabs of HEAD_SLAB batch rows, stage 2 sums the slabs.
+// Both stages carry a compensation term (Neumaier), and stage 1 also keeps
+// the fp32 rounding error of each product (zero for bf16 inputs, whose
+// products are exact in fp32), so the result does not depend on B beyond
+// the last bit or two.
+// ---------------------------------------------------------------------------
+constexpr int HEAD_SLAB = 64;
+
+struct CompSum {
+    float s = 0.0f, c = 0.0f;
+    FMDA_DEV void add(float v) {
+#pragma clang fp contract(off)
+        const float t = s + v;
+        // the smaller-magnitude operand's low bits are what t dropped
+        c += fabsf(s) >= fabsf(v) ? (s - t) + v : (v - t) + s;
+        s = t;
+    }
+    FMDA_DEV float value() const { return s + c; }
+};
+
+// grid (ceil(K/128), n_slabs, C), 128 threads: thread = one k column
+template <typename T>
+__global__ void head_wgrads_stage1_kernel(const float* __restrict__ dlogits,
+                                          const T* __restrict__ x,
+                                          float* __restrict__ dw_part,
+                                          float* __restrict__ db_part, int B,
+                                          int K, int C) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const int slab = blockIdx.y, c = blockIdx.z;
+    const int r0 = slab * HEAD_SLAB;
+    const int r1 = min(r0 + HEAD_SLAB, B);
+    CompSum dw, db;
+#pragma unroll 8
+    for (int r = r0; r < r1; ++r) {
+#pragma clang fp contract(off)
+        const float dl32 = dlogits[(long)r * C + c];
+        const float dl = round_to<T>(dl32);
+        const float xv = to_f32<T>(x[(long)r * K + k]);
+        const float p = dl * xv;                 // rounded product ...
+        dw.add(p);
+        dw.c += __builtin_fmaf(dl, xv, -p);      // ... and what it dropped
+        db.add(dl32);
+    }
+    dw_part[((long)slab * C + c) * K + k] = dw.value();
+    if (k == 0) db_part[slab * C + c] = db.value();
+}
+
+// one thread per dW element, then C threads for db
+__global__ void head_wgrads_stage2_kernel(const float* __restrict__ dw_part,
+                                          const float* __restrict__ db_part,
+                                          float* __restrict__ dW,
+                                          float* __restrict__ db, int n_slabs,
+                                          int K, int C) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n_w = C * K;
+    if (idx >= n_w + C) return;
+    CompSum a;
+    if (idx < n_w) {
+#pragma unroll 8
+        for (int s = 0; s < n_slabs; ++s) a.add(dw_part[(long)s * n_w + idx]);
+        dW[idx] = a.value();
+    } else {
+        const int c = idx - n_w;
+        for (int s = 0; s < n_slabs; ++s) a.add(db_part[s * C + c]);
+        db[c] = a.value();
+    }
+}
+
+inline int launch_ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+
+}  // namespace
+}  // namespace fmda
+
+using namespace fmda;
+
+extern "C" int fmda_pack_gru_layer_launch(
+        int is_bf16, const float* const* masters, void* w_ih_cat,
+        void* b_ih_cat, void* w_hh_cat, float* b_hh_cat, void* wt, int D,
+        int H, int Hp, int F, hipStream_t stream) {
+    // masters: [w_ih, w_hh, b_ih, b_hh] per direction
+    GruMasters m = {};
+    for (int d = 0; d < D; ++d) {
+        m.w_ih[d] = masters[4 * d + 0];
+        m.w_hh[d] = masters[4 * d + 1];
+        m.b_ih[d] = masters[4 * d + 2];
+        m.b_hh[d] = masters[4 * d + 3];
+    }
+    const long total = (long)D * 3 * Hp * ((long)F + 2L * Hp + 2);
+    const long blocks = (total + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048));
+    if (is_bf16)
+        pack_gru_layer_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
+            m, (__hip_bfloat16*)w_ih_cat, (__hip_bfloat16*)b_ih_cat,
+            (__hip_bfloat16*)w_hh_cat, b_hh_cat, (__hip_bfloat16*)wt, D, H,
+            Hp, F);
+    else
+        pack_gru_layer_kernel<float><<<grid, 256, 0, stream>>>(
+            m, (float*)w_ih_cat, (float*)b_ih_cat, (float*)w_hh_cat,
+            b_hh_cat, (float*)wt, D, H, Hp, F);
+    return launch_ok();
+}
+
+extern "C" int fmda_finalize_gru_wgrads_launch(
+        int part_bf16, const void* part_ih, int c_ih, const void* part_hh,
+        int c_hh, float* const* grads, int D, int H, int Hp, int F,
+        hipStream_t stream) {
+    // grads: [dw_ih, dw_hh] per direction
+    GruWgrads o = {};
+    for (int d = 0; d < D; ++d) {
+        o.dw_ih[d] = grads[2 * d + 0];
+        o.dw_hh[d] = grads[2 * d + 1];
+    }
+    const long total = (long)D * 3 * H * ((long)F + H);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (part_bf16)
+        finalize_gru_wgrads_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
+            (const __hip_bfloat16*)part_ih, c_ih,
+            (const __hip_bfloat16*)part_hh, c_hh, o, D, H, Hp, F);
+    else
+        finalize_gru_wgrads_kernel<float><<<grid, 256, 0, stream>>>(
+            (const float*)part_ih, c_ih, (const float*)part_hh, c_hh, o, D,
+            H, Hp, F);
+    return launch_ok();
+}
+
+extern "C" int fmda_head_fwd_master_launch(
+        int is_bf16, const void* x, const float* W, const float* bias,
+        const float* y, const float* wgt, const float* pw, float* logits,
+        float* sig, float* loss_sum, int B, int K, int C,
+        hipStream_t stream) {
+    // same launch shape as fmda_head_fwd_launch: the per-block loss
+    // partials (and their sum) must not change
+    const dim3 grid((B * C + 255) / 256);
+    if (is_bf16)
+        head_fwd_master_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
+            (const __hip_bfloat16*)x, W, bias, y, wgt, pw, logits, sig,
+            loss_sum, B, K, C);
+    else
+        head_fwd_master_kernel<float><<<grid, 256, 0, stream>>>(
+            (const float*)x, W, bias, y, wgt, pw, logits, sig, loss_sum, B,
+            K, C);
+    return launch_ok();
+}
+
+extern "C" int fmda_head_bwd_master_launch(
+        int is_bf16, const float* sig, const float* y, const float* wgt,
+        const float* pw, const float* gscale, const float* W,
+        float* dlogits, void* dx, int B, int K, int C, hipStream_t stream) {
+    const dim3 grid((B * K + 255) / 256);
+    if (is_bf16)
+        head_bwd_master_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
+            sig, y, wgt, pw, gscale, W, dlogits, (__hip_bfloat16*)dx, B, K,
+            C);
+    else
+        head_bwd_master_kernel<float><<<grid, 256, 0, stream>>>(
+            sig, y, wgt, pw, gscale, W, dlogits, (float*)dx, B, K, C);
+    return launch_ok();
+}
+
+extern "C" int fmda_head_wgrads_slabs(int B) {
+    return (B + HEAD_SLAB - 1) / HEAD_SLAB;
+}
+
+extern "C" int fmda_head_wgrads_launch(
+        int is_bf16, const float* dlogits, const void* x, float* dw_part,
+        float* db_part, float* dW, float* db, int B, int K, int C,
+        hipStream_t stream) {
+    const int n_slabs = fmda_head_wgrads_slabs(B);
+    const dim3 grid1((K + 127) / 128, n_slabs, C);
+    if (is_bf16)
+        head_wgrads_stage1_kernel<__hip_bfloat16><<<grid1, 128, 0, stream>>>(
+            dlogits, (const __hip_bfloat16*)x, dw_part, db_part, B, K, C);
+    else
+        head_wgrads_stage1_kernel<float><<<grid1, 128, 0, stream>>>(
+            dlogits, (const float*)x, dw_part, db_part, B, K, C);
+    if (launch_ok() != 0) return -1;
+    const dim3 grid2((C * K + C + 255) / 256);
+    head_wgrads_stage2_kernel<<<grid2, 256, 0, stream>>>(
+        dw_part, db_part, dW, db, n_slabs, K, C);
+    return launch_ok();
+}

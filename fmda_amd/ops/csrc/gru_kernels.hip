@@ -2648,11 +2648,14 @@ extern "C" int fmda_spatial_dropout_launch(int is_bf16, const void* x,
 // One thread per (b, h): replaces four eager kernels (direction add, max
 // reduce, sum reduce, and the backward scatter) with one read / one write
 // pass over the (B, T, n_dir*H) activations.
+// OT is the type of the pooled outputs and GT that of their incoming
+// gradients: float, or the activation type T, which spares the caller a
+// cast kernel per tensor (the value is rounded once either way).
 // ===========================================================================
-template <typename T>
+template <typename T, typename OT>
 __global__ void pool_fwd_kernel(const T* __restrict__ out,
-                                float* __restrict__ maxv,
-                                float* __restrict__ avgv,
+                                OT* __restrict__ maxv,
+                                OT* __restrict__ avgv,
                                 int* __restrict__ amax, int B, int Tseq,
                                 int H, int n_dir) {
     // one thread per (b, h-pair): 4-byte loads keep the row reads at full
@@ -2681,24 +2684,27 @@ __global__ void pool_fwd_kernel(const T* __restrict__ out,
         if (v1 > mx1) { mx1 = v1; im1 = t; }
     }
     const int o = b * H + h2;
-    maxv[o] = mx0; maxv[o + 1] = mx1;
-    avgv[o] = s0 / (float)Tseq; avgv[o + 1] = s1 / (float)Tseq;
+    maxv[o] = from_f32<OT>(mx0); maxv[o + 1] = from_f32<OT>(mx1);
+    avgv[o] = from_f32<OT>(s0 / (float)Tseq);
+    avgv[o + 1] = from_f32<OT>(s1 / (float)Tseq);
     amax[o] = im0; amax[o + 1] = im1;
 }
 
-template <typename T>
-__global__ void pool_bwd_kernel(const float* __restrict__ dmax,
-                                const float* __restrict__ davg,
+template <typename T, typename GT>
+__global__ void pool_bwd_kernel(const GT* __restrict__ dmax,
+                                const GT* __restrict__ davg,
                                 const int* __restrict__ amax,
                                 T* __restrict__ dout, int B, int Tseq, int H,
-                                int n_dir) {
+                                int n_dir, long ld_max, long ld_avg) {
+    // ld_*: row pitch of dmax / davg in elements (column slices of the
+    // pooled-feature gradient are read in place)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * H) return;
     const int b = idx / H;
     const int h = idx % H;
     const int HD = n_dir * H;
-    const float ga = davg[idx] / (float)Tseq;
-    const float gm = dmax[idx];
+    const float ga = to_f32<GT>(davg[b * ld_avg + h]) / (float)Tseq;
+    const float gm = to_f32<GT>(dmax[b * ld_max + h]);
     const int im = amax[idx];
     T* p = dout + (long)b * Tseq * HD + h;
     for (int t = 0; t < Tseq; ++t) {
@@ -2712,9 +2718,10 @@ __global__ void pool_bwd_kernel(const float* __restrict__ dmax,
 // loads/stores — the pair kernels' 4-byte accesses ran at ~3.3 TB/s
 // against the 6.3 TB/s stream peak. Requires H % 8 == 0 (the pair kernels
 // stay as the fallback for odd hidden sizes).
+template <typename OT>
 __global__ void pool_fwd_oct_kernel(const __hip_bfloat16* __restrict__ out,
-                                    float* __restrict__ maxv,
-                                    float* __restrict__ avgv,
+                                    OT* __restrict__ maxv,
+                                    OT* __restrict__ avgv,
                                     int* __restrict__ amax, int B, int Tseq,
                                     int H, int n_dir) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2744,17 +2751,19 @@ __global__ void pool_fwd_oct_kernel(const __hip_bfloat16* __restrict__ out,
     const int o = b * H + h8;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        maxv[o + k] = mx[k];
-        avgv[o + k] = s[k] / (float)Tseq;
+        maxv[o + k] = from_f32<OT>(mx[k]);
+        avgv[o + k] = from_f32<OT>(s[k] / (float)Tseq);
         amax[o + k] = im[k];
     }
 }
 
-__global__ void pool_bwd_oct_kernel(const float* __restrict__ dmax,
-                                    const float* __restrict__ davg,
+template <typename GT>
+__global__ void pool_bwd_oct_kernel(const GT* __restrict__ dmax,
+                                    const GT* __restrict__ davg,
                                     const int* __restrict__ amax,
                                     __hip_bfloat16* __restrict__ dout,
-                                    int B, int Tseq, int H, int n_dir) {
+                                    int B, int Tseq, int H, int n_dir,
+                                    long ld_max, long ld_avg) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int H8 = H / 8;
     if (idx >= B * H8) return;
@@ -2765,8 +2774,8 @@ __global__ void pool_bwd_oct_kernel(const float* __restrict__ dmax,
     int im[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        ga[k] = davg[o + k] / (float)Tseq;
-        gm[k] = dmax[o + k];
+        ga[k] = to_f32<GT>(davg[b * ld_avg + h8 + k]) / (float)Tseq;
+        gm[k] = to_f32<GT>(dmax[b * ld_max + h8 + k]);
         im[k] = amax[o + k];
     }
     const int HD = n_dir * H;
@@ -2787,10 +2796,10 @@ __global__ void pool_bwd_oct_kernel(const float* __restrict__ dmax,
 // per (b, h-pair), lanes strided over T, max/argmax/sum combined with
 // shfl_xor reductions. Argmax tie-break keeps the smallest t — exactly the
 // sequential kernel's first-strictly-greater scan.
-template <typename T>
+template <typename T, typename OT>
 __global__ void pool_fwd_small_kernel(const T* __restrict__ out,
-                                      float* __restrict__ maxv,
-                                      float* __restrict__ avgv,
+                                      OT* __restrict__ maxv,
+                                      OT* __restrict__ avgv,
                                       int* __restrict__ amax, int B, int Tseq,
                                       int H, int n_dir) {
     const int HP2 = H / 2;
@@ -2829,62 +2838,103 @@ __global__ void pool_fwd_small_kernel(const T* __restrict__ out,
     }
     if (lane == 0) {
         const int o = b * H + h2;
-        maxv[o] = mx0; maxv[o + 1] = mx1;
-        avgv[o] = s0 / (float)Tseq; avgv[o + 1] = s1 / (float)Tseq;
+        maxv[o] = from_f32<OT>(mx0); maxv[o + 1] = from_f32<OT>(mx1);
+        avgv[o] = from_f32<OT>(s0 / (float)Tseq);
+        avgv[o + 1] = from_f32<OT>(s1 / (float)Tseq);
         amax[o] = im0; amax[o + 1] = im1;
     }
 }
 
-extern "C" int fmda_pool_fwd_launch(int is_bf16, const void* out, float* maxv,
-                                    float* avgv, int* amax, int B, int Tseq,
-                                    int H, int n_dir, hipStream_t stream) {
+// act_io != 0 (bf16 only): maxv / avgv are bf16 like the activations.
+extern "C" int fmda_pool_fwd_launch(int is_bf16, const void* out, void* maxv,
+                                    void* avgv, int* amax, int B, int Tseq,
+                                    int H, int n_dir, int act_io,
+                                    hipStream_t stream) {
+    using bf16 = __hip_bfloat16;
+    if (act_io && !is_bf16) return -2;
     const int n = B * (H / 2);   // thread per h-pair (H is always even)
     if (n < 4096) {
         // small grid (streaming predict): wave per pair, lanes over T
         const dim3 grid((n + 3) / 4);
-        if (is_bf16)
-            pool_fwd_small_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
-                (const __hip_bfloat16*)out, maxv, avgv, amax, B, Tseq, H,
+        if (act_io)
+            pool_fwd_small_kernel<bf16, bf16><<<grid, 256, 0, stream>>>(
+                (const bf16*)out, (bf16*)maxv, (bf16*)avgv, amax, B, Tseq, H,
                 n_dir);
+        else if (is_bf16)
+            pool_fwd_small_kernel<bf16, float><<<grid, 256, 0, stream>>>(
+                (const bf16*)out, (float*)maxv, (float*)avgv, amax, B, Tseq,
+                H, n_dir);
         else
-            pool_fwd_small_kernel<float><<<grid, 256, 0, stream>>>(
-                (const float*)out, maxv, avgv, amax, B, Tseq, H, n_dir);
+            pool_fwd_small_kernel<float, float><<<grid, 256, 0, stream>>>(
+                (const float*)out, (float*)maxv, (float*)avgv, amax, B, Tseq,
+                H, n_dir);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     if (is_bf16 && H % 8 == 0) {
         const int n8 = B * (H / 8);
-        pool_fwd_oct_kernel<<<dim3((n8 + 255) / 256), 256, 0, stream>>>(
-            (const __hip_bfloat16*)out, maxv, avgv, amax, B, Tseq, H, n_dir);
+        const dim3 grid8((n8 + 255) / 256);
+        if (act_io)
+            pool_fwd_oct_kernel<bf16><<<grid8, 256, 0, stream>>>(
+                (const bf16*)out, (bf16*)maxv, (bf16*)avgv, amax, B, Tseq, H,
+                n_dir);
+        else
+            pool_fwd_oct_kernel<float><<<grid8, 256, 0, stream>>>(
+                (const bf16*)out, (float*)maxv, (float*)avgv, amax, B, Tseq,
+                H, n_dir);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     const dim3 grid((n + 255) / 256);
-    if (is_bf16)
-        pool_fwd_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
-            (const __hip_bfloat16*)out, maxv, avgv, amax, B, Tseq, H, n_dir);
+    if (act_io)
+        pool_fwd_kernel<bf16, bf16><<<grid, 256, 0, stream>>>(
+            (const bf16*)out, (bf16*)maxv, (bf16*)avgv, amax, B, Tseq, H,
+            n_dir);
+    else if (is_bf16)
+        pool_fwd_kernel<bf16, float><<<grid, 256, 0, stream>>>(
+            (const bf16*)out, (float*)maxv, (float*)avgv, amax, B, Tseq, H,
+            n_dir);
     else
-        pool_fwd_kernel<float><<<grid, 256, 0, stream>>>(
-            (const float*)out, maxv, avgv, amax, B, Tseq, H, n_dir);
+        pool_fwd_kernel<float, float><<<grid, 256, 0, stream>>>(
+            (const float*)out, (float*)maxv, (float*)avgv, amax, B, Tseq, H,
+            n_dir);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-extern "C" int fmda_pool_bwd_launch(int is_bf16, const float* dmax,
-                                    const float* davg, const int* amax,
+// act_io != 0 (bf16 only): dmax / davg are bf16 like the activations.
+// ld_max / ld_avg: their row pitches in elements (H when contiguous).
+extern "C" int fmda_pool_bwd_launch(int is_bf16, const void* dmax,
+                                    const void* davg, const int* amax,
                                     void* dout, int B, int Tseq, int H,
-                                    int n_dir, hipStream_t stream) {
+                                    int n_dir, int act_io, long ld_max,
+                                    long ld_avg, hipStream_t stream) {
+    using bf16 = __hip_bfloat16;
+    if (act_io && !is_bf16) return -2;
     const int n = B * H;
     if (is_bf16 && H % 8 == 0 && B * (H / 8) >= 4096) {
         const int n8 = B * (H / 8);
-        pool_bwd_oct_kernel<<<dim3((n8 + 255) / 256), 256, 0, stream>>>(
-            dmax, davg, amax, (__hip_bfloat16*)dout, B, Tseq, H, n_dir);
+        const dim3 grid8((n8 + 255) / 256);
+        if (act_io)
+            pool_bwd_oct_kernel<bf16><<<grid8, 256, 0, stream>>>(
+                (const bf16*)dmax, (const bf16*)davg, amax, (bf16*)dout, B,
+                Tseq, H, n_dir, ld_max, ld_avg);
+        else
+            pool_bwd_oct_kernel<float><<<grid8, 256, 0, stream>>>(
+                (const float*)dmax, (const float*)davg, amax, (bf16*)dout, B,
+                Tseq, H, n_dir, ld_max, ld_avg);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     const dim3 grid((n + 255) / 256);
-    if (is_bf16)
-        pool_bwd_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
-            dmax, davg, amax, (__hip_bfloat16*)dout, B, Tseq, H, n_dir);
+    if (act_io)
+        pool_bwd_kernel<bf16, bf16><<<grid, 256, 0, stream>>>(
+            (const bf16*)dmax, (const bf16*)davg, amax, (bf16*)dout, B, Tseq,
+            H, n_dir, ld_max, ld_avg);
+    else if (is_bf16)
+        pool_bwd_kernel<bf16, float><<<grid, 256, 0, stream>>>(
+            (const float*)dmax, (const float*)davg, amax, (bf16*)dout, B,
+            Tseq, H, n_dir, ld_max, ld_avg);
     else
-        pool_bwd_kernel<float><<<grid, 256, 0, stream>>>(
-            dmax, davg, amax, (float*)dout, B, Tseq, H, n_dir);
+        pool_bwd_kernel<float, float><<<grid, 256, 0, stream>>>(
+            (const float*)dmax, (const float*)davg, amax, (float*)dout, B,
+            Tseq, H, n_dir, ld_max, ld_avg);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

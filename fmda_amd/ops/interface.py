@@ -17,7 +17,8 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import load_extension
-from .blas import chunked_colsum, chunked_outer, enable_tunableop
+from .blas import (chunked_colsum, chunked_outer, chunked_outer_parts,
+                   enable_tunableop)
 
 # Minimum padded hidden is 32: the bf16 recurrence tiles MFMA K=32, so
 # Hp=16 would give a ZERO-trip GEMM loop (caught by the randomized shape
@@ -30,6 +31,33 @@ def _pad_h(H: int) -> int:
         if H <= hp:
             return hp
     raise ValueError(f"hidden size {H} > {_ALLOWED_HP[-1]} not supported")
+
+
+def _glue_mode() -> int:
+    """FMDA_NATIVE_GLUE, read per call:
+    1 (default): weight packing, the head's read of the fp32 masters and
+       the pooling casts run as single HIP kernels (csrc/glue_kernels.hip).
+       Every one of these steps is exact, so a training step computes what
+       the eager formulation computes, bit for bit.
+    2: also the weight-gradient reductions (finalize_gru_wgrads,
+       head_wgrads). They sum in fp32 in their own fixed order, and the
+       head's dW / db skip the round trip through bf16, so gradients differ
+       from the eager ones in the last bits (fewer launches, not the same
+       numbers).
+    0: the eager torch formulation of all of it (A/B runs on one build)."""
+    return {"0": 0, "2": 2}.get(os.environ.get("FMDA_NATIVE_GLUE", "1"), 1)
+
+
+def _native_glue() -> bool:
+    return _glue_mode() >= 1
+
+
+def _native_reductions() -> bool:
+    return _glue_mode() == 2
+
+
+def _fp32_cuda(*tensors) -> bool:
+    return all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
 
 
 def _pad_gate_rows(w: torch.Tensor, H: int, Hp: int) -> torch.Tensor:
@@ -53,6 +81,35 @@ def _pad_cols(w: torch.Tensor, H: int, Hp: int) -> torch.Tensor:
     out = w.new_zeros(shape)
     out[..., :H] = w
     return out
+
+
+def _pack_layer_eager(params, H: int, Hp: int, dtype):
+    """Eager pack of one layer. params: per direction (w_ih, w_hh, b_ih,
+    b_hh). Returns w_ih_cat (D*3Hp, F), b_ih_cat (D*3Hp), w_hh_cat
+    (D, 3Hp, Hp) in `dtype` and b_hh_cat (D, 3Hp) in fp32."""
+    w_ihs, w_hhs, b_ihs, b_hhs = [], [], [], []
+    for (w_ih, w_hh, b_ih, b_hh) in params:
+        w_ihs.append(_pad_gate_rows(w_ih, H, Hp))
+        w_hhs.append(_pad_cols(_pad_gate_rows(w_hh, H, Hp), H, Hp))
+        b_ihs.append(_pad_gate_rows(b_ih, H, Hp))
+        b_hhs.append(_pad_gate_rows(b_hh, H, Hp))
+    return (torch.cat(w_ihs, dim=0).to(dtype),
+            torch.cat(b_ihs, dim=0).to(dtype),
+            torch.stack(w_hhs, dim=0).to(dtype).contiguous(),
+            torch.stack(b_hhs, dim=0).float().contiguous())
+
+
+def _pack_layer(params, H: int, Hp: int, dtype):
+    """(w_ih_cat, b_ih_cat, w_hh_cat, b_hh_cat, wt) for one layer: one HIP
+    kernel from the fp32 masters, which also emits wt = W_hh^T (D, Hp, 3Hp)
+    for the BPTT kernel; the eager pack (wt None: gru_bwd transposes
+    itself) for other master dtypes or FMDA_NATIVE_GLUE=0."""
+    flat = [t for four in params for t in four]
+    if (_native_glue() and _fp32_cuda(*flat)
+            and dtype in (torch.bfloat16, torch.float32)):
+        return tuple(load_extension().pack_gru_layer(
+            [t.detach().contiguous() for t in flat], Hp, dtype))
+    return _pack_layer_eager(params, H, Hp, dtype) + (None,)
 
 
 class _GRURecurrence(torch.autograd.Function):
@@ -207,18 +264,28 @@ class _DirSumPool(torch.autograd.Function):
     def forward(ctx, out, n_dir):
         ext = load_extension()
         out = out.contiguous()
-        maxv, avgv, amax = ext.pool_fwd(out, n_dir)
+        # native: the kernels emit max / avg and take their grads in the
+        # activation dtype (same rounding points, four cast kernels fewer)
+        native = _native_glue()
+        maxv, avgv, amax = ext.pool_fwd(out, n_dir, native)
         ctx.save_for_backward(amax)
-        ctx.meta = (out.shape[1], n_dir, out.dtype)
+        ctx.meta = (out.shape[1], n_dir, out.dtype, native)
         return maxv.to(out.dtype), avgv.to(out.dtype)
 
     @staticmethod
     def backward(ctx, dmax, davg):
         ext = load_extension()
         (amax,) = ctx.saved_tensors
-        T, n_dir, dtype = ctx.meta
-        dout = ext.pool_bwd(dmax.float().contiguous(),
-                            davg.float().contiguous(), amax, T, n_dir, dtype)
+        T, n_dir, dtype, native = ctx.meta
+        if native and dmax.dtype == dtype and davg.dtype == dtype:
+            # column slices of the (B, 3H) feature gradient are read in
+            # place through their row pitch
+            if any(g.stride(1) != 1 or g.stride(0) < g.shape[1]
+                   for g in (dmax, davg)):
+                dmax, davg = dmax.contiguous(), davg.contiguous()
+        else:
+            dmax, davg = dmax.float().contiguous(), davg.float().contiguous()
+        dout = ext.pool_bwd(dmax, davg, amax, T, n_dir, dtype)
         return dout, None
 
 
@@ -258,9 +325,54 @@ class _HeadLoss(torch.autograd.Function):
         return dx, dW, db, None, None, None
 
 
+class _HeadLossMaster(torch.autograd.Function):
+    """_HeadLoss with the fp32 master W / b as the differentiable inputs:
+    the kernels round them to x's dtype in registers (loss, logits and dx
+    are bit-identical to _HeadLoss on the cast copies), so the two cast
+    kernels of the forward go. dW / db are, by default, computed and
+    rounded exactly as _HeadLoss plus autograd's cast-back would; with
+    FMDA_NATIVE_GLUE=2 they come in fp32 from one two-stage reduction over
+    the batch (no bf16 rounding: close to, not equal to, the default)."""
+
+    @staticmethod
+    def forward(ctx, x2d, W, b, y, wgt, pw):
+        ext = load_extension()
+        ctx.native_reductions = _native_reductions()
+        x2d = x2d.contiguous()
+        W = W.contiguous()
+        y, wgt, pw = y.contiguous(), wgt.contiguous(), pw.contiguous()
+        logits, sig, loss_sum = ext.head_loss_fwd_master(
+            x2d, W, b.contiguous(), y, wgt, pw)
+        B, C = logits.shape
+        loss = (loss_sum / float(B * C)).reshape(())
+        ctx.save_for_backward(x2d, W, y, wgt, pw, sig)
+        ctx.mark_non_differentiable(logits)
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits):
+        ext = load_extension()
+        x2d, W, y, wgt, pw, sig = ctx.saved_tensors
+        dlogits, dx = ext.head_loss_bwd_master(
+            sig, y, wgt, pw, dloss.reshape(1).float().contiguous(), W,
+            x2d.dtype)
+        if ctx.native_reductions:
+            dW, db = ext.head_wgrads(dlogits, x2d)
+        else:
+            # _HeadLoss.backward on the cast copies, then the cast-back of
+            # W.to(dtype) / b.to(dtype): the same values, rounding included
+            dW = chunked_outer(dlogits.to(x2d.dtype), x2d).to(W.dtype)
+            db = dlogits.sum(dim=0).to(x2d.dtype).to(W.dtype)
+        return dx, dW, db, None, None, None
+
+
 def fused_head_loss(x2d, weight, bias, y, wgt, pw):
     """(loss, logits) for the reference head + class-weighted BCE
     (biGRU_model.py:137 + notebook cell 29 loss)."""
+    if (_native_glue() and x2d.is_cuda and _fp32_cuda(weight, bias)
+            and x2d.dtype in (torch.bfloat16, torch.float32)):
+        return _HeadLossMaster.apply(x2d, weight, bias, y.float(),
+                                     wgt.float(), pw.float())
     Wc = weight.to(x2d.dtype)
     bc = bias.to(x2d.dtype)
     return _HeadLoss.apply(x2d, Wc, bc, y.float(), wgt.float(), pw.float())
@@ -290,20 +402,14 @@ class _BiGRULayer(torch.autograd.Function):
         H = w_hh0.shape[1]
         dtype = x.dtype
         B, T, F = x.shape
+        params = [(w_ih0, w_hh0, b_ih0, b_hh0)]
+        if D == 2:
+            params.append((w_ih1, w_hh1, b_ih1, b_hh1))
         with torch.no_grad():
-            w_ihs = [_pad_gate_rows(w_ih0, H, Hp)]
-            w_hhs = [_pad_cols(_pad_gate_rows(w_hh0, H, Hp), H, Hp)]
-            b_ihs = [_pad_gate_rows(b_ih0, H, Hp)]
-            b_hhs = [_pad_gate_rows(b_hh0, H, Hp)]
-            if D == 2:
-                w_ihs.append(_pad_gate_rows(w_ih1, H, Hp))
-                w_hhs.append(_pad_cols(_pad_gate_rows(w_hh1, H, Hp), H, Hp))
-                b_ihs.append(_pad_gate_rows(b_ih1, H, Hp))
-                b_hhs.append(_pad_gate_rows(b_hh1, H, Hp))
-            w_ih_cat = torch.cat(w_ihs, dim=0).to(dtype)       # (D*3Hp, F)
-            b_ih_cat = torch.cat(b_ihs, dim=0).to(dtype)
-            w_hh_cat = torch.stack(w_hhs, dim=0).to(dtype)     # (D, 3Hp, Hp)
-            b_hh_cat = torch.stack(b_hhs, dim=0).float()       # (D, 3Hp)
+            # w_ih_cat (D*3Hp, F), b_ih_cat (D*3Hp), w_hh_cat (D, 3Hp, Hp),
+            # b_hh_cat (D, 3Hp) fp32, wt (D, Hp, 3Hp) or None
+            w_ih_cat, b_ih_cat, w_hh_cat, b_hh_cat, wt = _pack_layer(
+                params, H, Hp, dtype)
         x2d = x.reshape(B * T, F)
         gi = torch.addmm(b_ih_cat, x2d, w_ih_cat.t()).view(B, T, -1)
         h0c = h0.detach().contiguous() if h0 is not None else None
@@ -314,9 +420,10 @@ class _BiGRULayer(torch.autograd.Function):
         res = ext.gru_fwd(gi, w_hh_cat, b_hh_cat, h0c, out_drop_p,
                           out_drop_seed)
         out, h_last = res[0], res[1]
-        ctx.save_for_backward(x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out)
+        ctx.save_for_backward(x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out, wt)
         ctx.h0 = h0c
         ctx.meta = (D, H, Hp, out_drop_p, out_drop_seed)
+        ctx.native_reductions = _native_reductions()
         ctx.set_materialize_grads(False)
         if len(res) > 2:
             return out, h_last, res[2]
@@ -325,7 +432,7 @@ class _BiGRULayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out, d_hlast, d_outdrop=None):
         ext = load_extension()
-        x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out = ctx.saved_tensors
+        x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out, wt = ctx.saved_tensors
         D, H, Hp, drop_p, drop_seed = ctx.meta
         need_dx = ctx.needs_input_grad[0]
         if drop_p > 0:
@@ -342,44 +449,57 @@ class _BiGRULayer(torch.autograd.Function):
         d_out = d_out.contiguous().to(gi.dtype)
         d_hlast = d_hlast.contiguous().float()
         h0c = ctx.h0
+        # wt (from the native pack) spares gru_bwd its own transpose
         res = ext.gru_bwd(gi, w_hh_cat, b_hh_cat, out, d_out, d_hlast,
-                          drop_p, drop_seed, h0c)
+                          drop_p, drop_seed, h0c, wt)
         dgi, dgh, dh0_out, dbhh, dbih = res[:5]
         dgh0 = res[5] if len(res) > 5 else None
         M = dgi.shape[0] * dgi.shape[1]
-
-        # dW_hh via the time-shifted dGh and one split-K reduction
-        # (fp32 out: the grads feed fp32 masters, skip the bf16 round trip)
-        cross = chunked_outer(dgh.reshape(M, -1), out.reshape(M, -1),
-                              out_fp32=True)
-        if dgh0 is not None:
-            # t=0 term of dW_hh: dGh_0 (x) h0 (boundary slot holds zeros)
-            for d in range(D):
-                cross[d * 3 * Hp:(d + 1) * 3 * Hp,
-                      d * Hp:(d + 1) * Hp] += dgh0[d].float().t() @ h0c[d]
-        # dW_ih for both directions in one split-K reduction
-        dwih_cat = chunked_outer(dgi.reshape(M, -1), x2d, out_fp32=True)
         dx = None
         if need_dx:
             dx = torch.matmul(dgi.reshape(M, -1), w_ih_cat)
             dx = dx.view(dgi.shape[0], dgi.shape[1], -1)
+        dh0_grad = dh0_out if h0c is not None else None
 
-        grads = []
-        for d in range(D):
-            dwih = dwih_cat[d * 3 * Hp:(d + 1) * 3 * Hp]
-            # the column-block slice is non-contiguous; the fused optimizer
-            # (and DDP flattening) need contiguous grads
-            dwhh = cross[d * 3 * Hp:(d + 1) * 3 * Hp,
-                         d * Hp:(d + 1) * Hp].contiguous()
-            grads.append((
-                _unpad_gate_rows(dwih, H, Hp),
-                _unpad_gate_rows(dwhh, H, Hp)[:, :H],
-                _unpad_gate_rows(dbih[d], H, Hp),
-                _unpad_gate_rows(dbhh[d], H, Hp)))
+        if wt is not None and ctx.native_reductions and dgh0 is None:
+            # FMDA_NATIVE_GLUE=2: the split-K partials of dGi^T x and
+            # dGh^T out go straight to one kernel that sums the chunks in
+            # fp32 (ascending, not torch's order) and writes the four
+            # contiguous master-shaped grads; it reads only the diagonal
+            # direction blocks of the dW_hh partials
+            wg = ext.finalize_gru_wgrads(
+                chunked_outer_parts(dgi.reshape(M, -1), x2d),
+                chunked_outer_parts(dgh.reshape(M, -1), out.reshape(M, -1)),
+                D, H, Hp)
+            wgrads = [(wg[2 * d], wg[2 * d + 1]) for d in range(D)]
+        else:
+            # dW_hh via the time-shifted dGh and one split-K reduction (fp32
+            # out: the grads feed fp32 masters, skip the bf16 round trip)
+            cross = chunked_outer(dgh.reshape(M, -1), out.reshape(M, -1),
+                                  out_fp32=True)
+            if dgh0 is not None:
+                # t=0 term of dW_hh: dGh_0 (x) h0 (boundary slot holds zeros)
+                for d in range(D):
+                    cross[d * 3 * Hp:(d + 1) * 3 * Hp,
+                          d * Hp:(d + 1) * Hp] += dgh0[d].float().t() @ h0c[d]
+            # dW_ih for both directions in one split-K reduction
+            dwih_cat = chunked_outer(dgi.reshape(M, -1), x2d, out_fp32=True)
+            wgrads = []
+            for d in range(D):
+                dwih = dwih_cat[d * 3 * Hp:(d + 1) * 3 * Hp]
+                # the column-block slice is non-contiguous; the fused
+                # optimizer (and DDP flattening) need contiguous grads
+                dwhh = cross[d * 3 * Hp:(d + 1) * 3 * Hp,
+                             d * Hp:(d + 1) * Hp].contiguous()
+                wgrads.append((_unpad_gate_rows(dwih, H, Hp),
+                               _unpad_gate_rows(dwhh, H, Hp)[:, :H]))
+
+        grads = [wgrads[d] + (_unpad_gate_rows(dbih[d], H, Hp),
+                              _unpad_gate_rows(dbhh[d], H, Hp))
+                 for d in range(D)]
         if D == 1:
             grads.append((None, None, None, None))
         (a0, b0, c0, e0), (a1, b1, c1, e1) = grads
-        dh0_grad = dh0_out if h0c is not None else None
         return (dx, None, a0, b0, c0, e0, a1, b1, c1, e1, None, None,
                 dh0_grad)
 
@@ -405,16 +525,7 @@ def _packed_inference_weights(gru_module, layer, params, Hp, H, dtype):
     ent = getattr(gru_module, key, None)
     if ent is not None and ent[0] == versions:
         return ent[1]
-    w_ihs, w_hhs, b_ihs, b_hhs = [], [], [], []
-    for (w_ih, w_hh, b_ih, b_hh) in params:
-        w_ihs.append(_pad_gate_rows(w_ih, H, Hp))
-        w_hhs.append(_pad_cols(_pad_gate_rows(w_hh, H, Hp), H, Hp))
-        b_ihs.append(_pad_gate_rows(b_ih, H, Hp))
-        b_hhs.append(_pad_gate_rows(b_hh, H, Hp))
-    packed = (torch.cat(w_ihs, dim=0).to(dtype),
-              torch.cat(b_ihs, dim=0).to(dtype),
-              torch.stack(w_hhs, dim=0).to(dtype).contiguous(),
-              torch.stack(b_hhs, dim=0).float().contiguous())
+    packed = _pack_layer(params, H, Hp, dtype)[:4]
     setattr(gru_module, key, (versions, packed))
     return packed
 

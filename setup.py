@@ -23,6 +23,7 @@ setup(
             sources=[
                 "fmda_amd/ops/csrc/bindings.cpp",
                 "fmda_amd/ops/csrc/gru_kernels.hip",
+                "fmda_amd/ops/csrc/glue_kernels.hip",
                 "fmda_amd/ops/csrc/optim_kernels.hip",
                 "fmda_amd/ops/csrc/checkpoint.cpp",
             ],
