@@ -91,6 +91,9 @@ class TrainConfig:
     epochs: int = 25
     device: str = "cpu"
     dtype: str = "fp32"          # "fp32" | "bf16" (GPU compute dtype)
+    # validate / test each chunk as one table (BiGRU.evaluate_windows):
+    # layer-0 projections shared by overlapping windows, no DataLoader
+    windowed_eval: bool = False
 
 
 @dataclass

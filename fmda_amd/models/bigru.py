@@ -75,7 +75,10 @@ class BiGRU(nn.Module):
                 hidden: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Forward pass; returns (B, output_size) logits
         (semantics of biGRU_model.py:63-138)."""
-        concat_out = self.forward_features(input_seq, hidden)
+        return self._head(self.forward_features(input_seq, hidden))
+
+    def _head(self, concat_out: torch.Tensor) -> torch.Tensor:
+        """Linear head on the pooled (B, 3H) features -> logits."""
         if concat_out.dtype != self.linear.weight.dtype:
             # bf16 compute path with fp32 master weights: cast the head.
             return F.linear(concat_out, self.linear.weight.to(concat_out.dtype),
@@ -87,9 +90,6 @@ class BiGRU(nn.Module):
         """Everything before the linear head: returns the pooled concat
         (B, 3H) feature vector — the input of the reference's linear head
         (biGRU_model.py:133-137). Used by the fused head+loss kernel."""
-        batch_size = input_seq.size(0)
-        input_length = input_seq.size(1)
-
         if self.spatial_dropout:
             if (self.training and input_seq.is_cuda
                     and input_seq.dtype == torch.bfloat16
@@ -114,13 +114,20 @@ class BiGRU(nn.Module):
             gru_out, h_n = self._gru_hip(input_seq, hidden)
         else:
             gru_out, h_n = self.gru(input_seq, hidden)
+        return self._pool_concat(gru_out, h_n)
 
-        # 3-way pooling head (biGRU_model.py:108-137).
+    def _pool_concat(self, gru_out: torch.Tensor,
+                     h_n: torch.Tensor) -> torch.Tensor:
+        """3-way pooling head (biGRU_model.py:108-137): concat of the
+        direction-summed last hidden state, max pool and avg pool over time
+        of gru_out (B, T, D*H) -> (B, 3H)."""
+        batch_size = gru_out.size(0)
+        input_length = gru_out.size(1)
         hidden_v = h_n.view(self.n_layers, self.n_directions, batch_size,
                             self.hidden_size)
         last_hidden = hidden_v[-1].sum(dim=0)
 
-        if input_seq.is_cuda and self.hidden_size % 2 == 0:
+        if gru_out.is_cuda and self.hidden_size % 2 == 0:
             # fused direction-sum + max/avg pooling HIP kernel (pairs
             # columns; odd H takes the eager path below)
             from ..ops.interface import dirsum_pool
@@ -139,6 +146,95 @@ class BiGRU(nn.Module):
         from ..ops.interface import bigru_stack
         return bigru_stack(x, self.gru, self.n_layers, self.bidirectional,
                            self.dropout_p, self.training, hidden)
+
+    # ------------------------ windowed inference ----------------------- #
+
+    def forward_windows(self, table: torch.Tensor, window: int,
+                        stride: int = 1,
+                        batch_windows: int = 4096) -> torch.Tensor:
+        """Logits (n_windows, output_size) of every sliding window of a
+        normalised (N, F) table: row i is what
+        forward(table[i*stride : i*stride + window][None]) returns in eval
+        mode. On the GPU the layer-0 input projections are computed once
+        per table row and shared by all windows that contain the row; the
+        windows are never materialised. `batch_windows` windows run per
+        launch, so layer outputs stay bounded. On CPU the table is unfolded
+        and goes through the ordinary forward, in the same batches."""
+        assert not self.training, "forward_windows is inference only: " \
+            "call model.eval() first"
+        assert table.dim() == 2 and table.size(1) == self.n_features, \
+            f"table must be (N, {self.n_features})"
+        assert window >= 1 and stride >= 1 and batch_windows >= 1
+        assert table.size(0) >= window, "table shorter than one window"
+        n_windows = (table.size(0) - window) // stride + 1
+        logits = []
+        with torch.no_grad():
+            gi_rows = None
+            if table.is_cuda:
+                from ..ops.interface import (bigru_stack_windows,
+                                             table_projections)
+                gi_rows = table_projections(table, self.gru,
+                                            self.bidirectional)
+            for w0 in range(0, n_windows, batch_windows):
+                nb = min(batch_windows, n_windows - w0)
+                r0 = w0 * stride
+                r1 = r0 + (nb - 1) * stride + window
+                if gi_rows is not None:
+                    gru_out, h_n = bigru_stack_windows(
+                        table[r0:r1], self.gru, self.n_layers,
+                        self.bidirectional, window, stride,
+                        gi_rows=gi_rows[r0:r1])
+                    logits.append(self._head(self._pool_concat(gru_out, h_n)))
+                else:
+                    x = table[r0:r1].unfold(0, window, stride)
+                    logits.append(self.forward(
+                        x.permute(0, 2, 1).contiguous()))
+        return torch.cat(logits, dim=0)
+
+    def window_batch_metrics(self, table: torch.Tensor,
+                             targets: torch.Tensor, window: int,
+                             batch_size: int):
+        """Per-batch metrics of the stride-1 windows of one normalised
+        (N, F) table, batched like a sequential DataLoader over the
+        windows: (accuracies, hamming losses, fbetas, pred, target), the
+        first three with one entry per consecutive group of `batch_size`
+        windows. The target of a window is the targets row of its last
+        timestep. A table shorter than one window has no batches."""
+        self.eval()
+        empty = torch.LongTensor()
+        if table.size(0) < window:
+            return [], [], [], empty, empty
+        table = table.to(self.device)
+        # CPU (the oracle path) forms exactly the DataLoader's batches; the
+        # GPU shares projections across larger launches
+        bw = max(batch_size, 4096) if table.is_cuda else batch_size
+        logits = self.forward_windows(table, window, batch_windows=bw)
+        pred_all = torch.sigmoid(logits) > 0.5
+        target_all = targets[window - 1:window - 1 + pred_all.size(0)].to(
+            self.device)
+        accuracies, hamm_losses, fbetas_list = [], [], []
+        for b0 in range(0, pred_all.size(0), batch_size):
+            acc, ham, fbeta = batch_metrics(target_all[b0:b0 + batch_size],
+                                            pred_all[b0:b0 + batch_size],
+                                            beta=0.5)
+            accuracies.append(float(acc))
+            hamm_losses.append(float(ham))
+            fbetas_list.append(fbeta.cpu().numpy())
+        return (accuracies, hamm_losses, fbetas_list,
+                pred_all.cpu().type(torch.LongTensor),
+                target_all.cpu().type(torch.LongTensor))
+
+    def evaluate_windows(self, table: torch.Tensor, targets: torch.Tensor,
+                         window: int, batch_size: int):
+        """evaluate_model over the stride-1 windows of one normalised
+        (N, F) table without materialising them: the same 5-tuple (mean
+        accuracy, mean Hamming loss, mean per-class fbeta, pred_total,
+        target_total) as evaluate_model over a sequential
+        DataLoader(BatchLoader(...), batch_size)."""
+        accs, hams, fbetas, pred_total, target_total = \
+            self.window_batch_metrics(table, targets, window, batch_size)
+        return (np.mean(accs), np.mean(hams), np.mean(fbetas, axis=0),
+                pred_total, target_total)
 
     # ---------------------- reference training API --------------------- #
 

@@ -2,6 +2,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <climits>
+#include <cstdint>
 #include <vector>
 
 extern "C" int fmda_gru_fwd_launch(int is_bf16, int Hp, const void* gi,
@@ -10,7 +12,7 @@ extern "C" int fmda_gru_fwd_launch(int is_bf16, int Hp, const void* gi,
                                    const float* h0, void* out_drop,
                                    unsigned int drop_thr, float drop_scale,
                                    unsigned long long drop_seed,
-                                   hipStream_t stream);
+                                   long gi_pitch, hipStream_t stream);
 extern "C" int fmda_gru_fwd_cs_launch(const void* gi, const void* w,
                                       const float* bhh, void* out,
                                       float* hlast, void* hpub,
@@ -19,7 +21,7 @@ extern "C" int fmda_gru_fwd_cs_launch(const void* gi, const void* w,
                                       unsigned int drop_thr,
                                       float drop_scale,
                                       unsigned long long drop_seed,
-                                      hipStream_t stream);
+                                      long gi_pitch, hipStream_t stream);
 extern "C" int fmda_gru_bwd_cs_launch(const void* gi, const void* w,
                                       const void* wt, const float* bhh,
                                       const void* out, const void* dout,
@@ -108,6 +110,9 @@ extern "C" int fmda_head_bwd_master_launch(
         int is_bf16, const float* sig, const float* y, const float* wgt,
         const float* pw, const float* gscale, const float* W,
         float* dlogits, void* dx, int B, int K, int C, hipStream_t stream);
+extern "C" int fmda_normalize_table_launch(
+        int out_bf16, const float* x, const float* xmin, const float* xmax,
+        void* y, long N, int F, hipStream_t stream);
 extern "C" int fmda_head_wgrads_slabs(int B);
 extern "C" int fmda_head_wgrads_launch(
         int is_bf16, const float* dlogits, const void* x, float* dw_part,
@@ -128,22 +133,28 @@ extern "C" int fmda_opt_adam_launch(const void* chunks, int n_chunks,
 
 namespace {
 
+// gi is the dense (B, T, n_dir*3Hp) tensor, or with `table` the
+// (R, n_dir*3Hp) table of per-row projections that gru_fwd_windows slides
+// over; B and T are then the caller's and stay untouched.
 void check_common(const torch::Tensor& gi, const torch::Tensor& w,
                   const torch::Tensor& bhh, int& B, int& T, int& n_dir,
-                  int& Hp, bool& is_bf16) {
+                  int& Hp, bool& is_bf16, bool table = false) {
     TORCH_CHECK(gi.is_cuda() && w.is_cuda() && bhh.is_cuda(),
                 "fmda gru: tensors must be on GPU");
     TORCH_CHECK(gi.is_contiguous() && w.is_contiguous() && bhh.is_contiguous(),
                 "fmda gru: tensors must be contiguous");
-    TORCH_CHECK(gi.dim() == 3 && w.dim() == 3, "fmda gru: bad ranks");
+    TORCH_CHECK(gi.dim() == (table ? 2 : 3) && w.dim() == 3,
+                "fmda gru: bad ranks");
     TORCH_CHECK(w.scalar_type() == gi.scalar_type(), "fmda gru: dtype mismatch");
     TORCH_CHECK(bhh.scalar_type() == torch::kFloat32, "bhh must be fp32");
     n_dir = w.size(0);
     Hp = w.size(2);
     TORCH_CHECK(w.size(1) == 3 * Hp, "w must be (n_dir, 3H, H)");
-    B = gi.size(0);
-    T = gi.size(1);
-    TORCH_CHECK(gi.size(2) == (int64_t)n_dir * 3 * Hp, "gi last dim mismatch");
+    if (!table) {
+        B = gi.size(0);
+        T = gi.size(1);
+    }
+    TORCH_CHECK(gi.size(-1) == (int64_t)n_dir * 3 * Hp, "gi last dim mismatch");
     TORCH_CHECK(n_dir == 1 || n_dir == 2, "n_dir must be 1 or 2");
     is_bf16 = gi.scalar_type() == torch::kBFloat16;
     TORCH_CHECK(is_bf16 || gi.scalar_type() == torch::kFloat32,
@@ -172,15 +183,18 @@ DropParams drop_params(double p) {
     return {(unsigned int)((float)p * 256.0f), (float)(1.0 / (1.0 - p))};
 }
 
-}  // namespace
-
-std::vector<torch::Tensor> gru_fwd(torch::Tensor gi, torch::Tensor w,
-                                   torch::Tensor bhh,
-                                   c10::optional<torch::Tensor> h0_opt,
-                                   double drop_p, int64_t drop_seed) {
-    int B, T, n_dir, Hp;
-    bool is_bf16;
-    check_common(gi, w, bhh, B, T, n_dir, Hp, is_bf16);
+// Forward dispatch shared by gru_fwd (dense gi, gi_pitch = T*n_dir*3Hp) and
+// gru_fwd_windows (table of projections, gi_pitch = stride*n_dir*3Hp).
+// gi_pitch is in elements; the kernels read 16-byte chunks through it.
+std::vector<torch::Tensor> gru_fwd_dispatch(
+        const torch::Tensor& gi, const torch::Tensor& w,
+        const torch::Tensor& bhh, int B, int T, int n_dir, int Hp,
+        bool is_bf16, int64_t gi_pitch,
+        const c10::optional<torch::Tensor>& h0_opt, double drop_p,
+        int64_t drop_seed) {
+    // a multiple of 16 bytes for every Hp the kernels take (Hp >= 16)
+    TORCH_CHECK((gi_pitch * gi.element_size()) % 16 == 0,
+                "fmda gru: gi batch pitch must be a multiple of 16 bytes");
     const float* h0 = nullptr;
     if (h0_opt.has_value()) {
         auto& h = h0_opt.value();
@@ -227,7 +241,7 @@ std::vector<torch::Tensor> gru_fwd(torch::Tensor gi, torch::Tensor w,
                                     n_dir, out_drop_ptr, drop_thr,
                                     drop_scale,
                                     (unsigned long long)drop_seed,
-                                    stream.stream());
+                                    (long)gi_pitch, stream.stream());
     } else {
         rc = fmda_gru_fwd_launch(is_bf16 ? 1 : 0, Hp, gi.data_ptr(),
                                  w.data_ptr(), bhh.data_ptr<float>(),
@@ -235,12 +249,53 @@ std::vector<torch::Tensor> gru_fwd(torch::Tensor gi, torch::Tensor w,
                                  n_dir, h0, out_drop_ptr, drop_thr,
                                  drop_scale,
                                  (unsigned long long)drop_seed,
-                                 stream.stream());
+                                 (long)gi_pitch, stream.stream());
     }
     TORCH_CHECK(rc == 0, "fmda gru_fwd launch failed rc=", rc, " Hp=", Hp);
     if (out_drop_ptr != nullptr)
         return {out, hlast, out_drop};
     return {out, hlast};
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> gru_fwd(torch::Tensor gi, torch::Tensor w,
+                                   torch::Tensor bhh,
+                                   c10::optional<torch::Tensor> h0_opt,
+                                   double drop_p, int64_t drop_seed) {
+    int B, T, n_dir, Hp;
+    bool is_bf16;
+    check_common(gi, w, bhh, B, T, n_dir, Hp, is_bf16);
+    return gru_fwd_dispatch(gi, w, bhh, B, T, n_dir, Hp, is_bf16,
+                            (int64_t)T * n_dir * 3 * Hp, h0_opt, drop_p,
+                            drop_seed);
+}
+
+// Recurrence over sliding windows of a table of input projections: window b
+// covers rows [b*stride, b*stride + T) of gi_rows (R, n_dir*3Hp), so
+// overlapping windows read the same rows instead of a materialised
+// (B, T, n_dir*3Hp) copy. B = (R - T) / stride + 1; trailing rows are
+// ignored. Same kernels and dispatch as gru_fwd with h0 = None and no
+// dropout; out (B, T, n_dir*Hp) and h_last (n_dir, B, Hp) as from gru_fwd.
+std::vector<torch::Tensor> gru_fwd_windows(torch::Tensor gi_rows,
+                                           torch::Tensor w, torch::Tensor bhh,
+                                           int64_t T, int64_t stride) {
+    int B = 0, T_ = 0, n_dir, Hp;
+    bool is_bf16;
+    check_common(gi_rows, w, bhh, B, T_, n_dir, Hp, is_bf16, true);
+    const int64_t R = gi_rows.size(0), row = gi_rows.size(1);
+    TORCH_CHECK(T >= 1 && stride >= 1,
+                "gru_fwd_windows: T and stride must be >= 1");
+    TORCH_CHECK(R >= T, "gru_fwd_windows: table has ", R,
+                " rows, fewer than the window T=", T);
+    const int64_t nB = (R - T) / stride + 1;
+    TORCH_CHECK(nB <= INT_MAX && T <= INT_MAX,
+                "gru_fwd_windows: too many windows");
+    // a row-slice of a larger table starts on a row boundary
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(gi_rows.data_ptr()) % 16 == 0,
+                "gru_fwd_windows: gi_rows must be 16-byte aligned");
+    return gru_fwd_dispatch(gi_rows, w, bhh, (int)nB, (int)T, n_dir, Hp,
+                            is_bf16, stride * row, c10::nullopt, 0.0, 0);
 }
 
 std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
@@ -535,6 +590,32 @@ torch::Tensor spatial_dropout_fused(torch::Tensor x, double p,
     return y;
 }
 
+// (N, F) fp32 raw table -> (nan_to_num(x, 0) - x_min) / (x_max - x_min) in
+// `dtype` (fp32 or bf16), one pass; bitwise what BatchLoader computes.
+torch::Tensor normalize_table(torch::Tensor x, torch::Tensor x_min,
+                              torch::Tensor x_max, torch::ScalarType dtype) {
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 &&
+                x.scalar_type() == torch::kFloat32,
+                "normalize_table: x must be a contiguous (N, F) fp32 GPU "
+                "tensor");
+    const int64_t N = x.size(0), F = x.size(1);
+    for (const torch::Tensor* t : {&x_min, &x_max})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == torch::kFloat32 && t->numel() == F,
+                    "normalize_table: x_min / x_max must be fp32 (F) on GPU");
+    TORCH_CHECK(dtype == torch::kBFloat16 || dtype == torch::kFloat32,
+                "normalize_table: dtype must be bf16 or fp32");
+    TORCH_CHECK(F >= 1 && F <= INT_MAX, "normalize_table: bad F");
+    auto y = torch::empty({N, F}, x.options().dtype(dtype));
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_normalize_table_launch(
+        dtype == torch::kBFloat16 ? 1 : 0, x.data_ptr<float>(),
+        x_min.data_ptr<float>(), x_max.data_ptr<float>(), y.data_ptr(),
+        (long)N, (int)F, stream.stream());
+    TORCH_CHECK(rc == 0, "normalize_table launch failed");
+    return y;
+}
+
 void ingest_row(torch::Tensor ring, torch::Tensor row, torch::Tensor xmin,
                 torch::Tensor xrng) {
     TORCH_CHECK(ring.is_cuda() && ring.is_contiguous() && ring.dim() == 2 &&
@@ -774,6 +855,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("gi"), py::arg("w"), py::arg("bhh"),
           py::arg("h0") = py::none(), py::arg("drop_p") = 0.0,
           py::arg("drop_seed") = 0);
+    m.def("gru_fwd_windows", &gru_fwd_windows,
+          "biGRU recurrence forward over sliding windows of a projection "
+          "table (shared rows, no materialised windows)",
+          py::arg("gi_rows"), py::arg("w"), py::arg("bhh"), py::arg("T"),
+          py::arg("stride") = 1);
+    m.def("normalize_table", &normalize_table,
+          "nan_to_num + min/max normalisation of a raw (N, F) table",
+          py::arg("x"), py::arg("x_min"), py::arg("x_max"), py::arg("dtype"));
     m.def("gru_bwd", &gru_bwd, "fused biGRU recurrence backward (HIP/CDNA4)",
           py::arg("gi"), py::arg("w"), py::arg("bhh"), py::arg("out"),
           py::arg("dout"), py::arg("dhT"), py::arg("drop_p") = 0.0,

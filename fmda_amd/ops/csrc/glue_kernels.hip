@@ -10,6 +10,8 @@
 //   head_*_master        classifier head + loss reading the fp32 masters
 //   head_wgrads          dW / db of the head, two-stage over the batch
 // All sums run in a fixed order: results are bitwise reproducible.
+// Inference side: normalize_table, the raw (N, F) table -> normalised
+// compute-dtype table in one pass (windowed evaluation of whole chunks).
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
@@ -309,6 +311,32 @@ __global__ void head_wgrads_stage2_kernel(const float* __restrict__ dw_part,
     }
 }
 
+// ===========================================================================
+// normalize_table
+// ===========================================================================
+// y[n][f] = T((nan_to_num(x[n][f]) - xmin[f]) / (xmax[f] - xmin[f])): the
+// table-sized counterpart of ingest_row_kernel, and bit for bit what
+// BatchLoader computes (nan_to_num(nan=0): NaN -> 0, +-inf -> +-FLT_MAX;
+// each of the two subtractions and the division rounded once in fp32, then
+// one rounding to T). Flat grid-stride walk over N*F elements.
+template <typename T>
+__global__ void normalize_table_kernel(const float* __restrict__ x,
+                                       const float* __restrict__ xmin,
+                                       const float* __restrict__ xmax,
+                                       T* __restrict__ y, long total, int F) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += stride) {
+        const int f = (int)(i % F);
+        float v = x[i];
+        if (v != v) v = 0.0f;
+        else if (v == __builtin_inff()) v = 3.402823466e+38f;
+        else if (v == -__builtin_inff()) v = -3.402823466e+38f;
+        const float mn = xmin[f];
+        y[i] = from_f32<T>(__fdiv_rn(__fsub_rn(v, mn), __fsub_rn(xmax[f], mn)));
+    }
+}
+
 inline int launch_ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 }  // namespace
@@ -397,6 +425,22 @@ extern "C" int fmda_head_bwd_master_launch(
     else
         head_bwd_master_kernel<float><<<grid, 256, 0, stream>>>(
             sig, y, wgt, pw, gscale, W, dlogits, (float*)dx, B, K, C);
+    return launch_ok();
+}
+
+extern "C" int fmda_normalize_table_launch(
+        int out_bf16, const float* x, const float* xmin, const float* xmax,
+        void* y, long N, int F, hipStream_t stream) {
+    const long total = N * (long)F;
+    if (total == 0) return 0;
+    const long blocks = (total + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
+    if (out_bf16)
+        normalize_table_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
+            x, xmin, xmax, (__hip_bfloat16*)y, total, F);
+    else
+        normalize_table_kernel<float><<<grid, 256, 0, stream>>>(
+            x, xmin, xmax, (float*)y, total, F);
     return launch_ok();
 }
 

@@ -270,6 +270,11 @@ FMDA_DEV bf16x8_t load_wfragB(const __hip_bfloat16* __restrict__ w, long pitch,
 // Forward kernel.
 //
 // gi:    (B, T, n_dir*3Hp)  input projections incl. b_ih (dtype T)
+// gi_pitch: elements between consecutive batch rows of gi. Dense gi has
+//        T*n_dir*3Hp; sliding windows over a table of per-row projections
+//        (window b starts at table row b*stride) have stride*n_dir*3Hp, so
+//        overlapping windows share their rows. Every forward family takes
+//        it; the time pitch n_dir*3Hp is the same in both layouts.
 // w:     (n_dir, 3Hp, Hp)   recurrent weights, row-major [n][k] (dtype T)
 // bhh:   (n_dir, 3Hp)       recurrent bias (fp32)
 // out:   (B, T, n_dir*Hp)   hidden states (dtype T; direction-concat layout)
@@ -282,7 +287,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
     const T* __restrict__ gi, const T* __restrict__ w,
     const float* __restrict__ bhh, T* __restrict__ out,
     float* __restrict__ hlast, int B, int Tseq, int n_dir,
-    const float* __restrict__ h0) {
+    const float* __restrict__ h0, long gi_pitch) {
     constexpr int NW = NT / 64;
     constexpr int MT = BT / 16;
     constexpr int NCT = Hp / 16;
@@ -330,7 +335,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
         if (IS_BF16) zero_tile<__hip_bfloat16, BT, NT>(hb_s, WP, tid);
     }
 
-    const long gi_row = (long)Tseq * n_dir * 3 * Hp;
+    const long gi_row = gi_pitch;   // elements between batch rows of gi
     const long out_row = (long)Tseq * n_dir * Hp;
     const T* gi_b = gi + (long)b0 * gi_row + (long)dir * 3 * Hp;
     T* out_b = out + (long)b0 * out_row + (long)dir * Hp;
@@ -915,7 +920,7 @@ void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
                        int n_dir, const float* __restrict__ h0,
                        __hip_bfloat16* __restrict__ out_drop,
                        unsigned int drop_thr, float drop_scale,
-                       unsigned long long drop_seed) {
+                       unsigned long long drop_seed, long gi_pitch) {
     constexpr int NW = NT / 64;
     constexpr int MT = BT / 16;
     constexpr int NCT = Hp / 16;
@@ -950,7 +955,7 @@ void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
     auto gi_buf = [&](int b) { return b ? gi_s1 : gi_s0; };
     auto hb_buf = [&](int b) { return b ? hb_s1 : hb_s0; };
 
-    const long gi_row = (long)Tseq * n_dir * 3 * Hp;
+    const long gi_row = gi_pitch;   // elements between batch rows of gi
     const long out_row = (long)Tseq * n_dir * Hp;
     const __hip_bfloat16* gi_b = gi + (long)b0 * gi_row + (long)dir * 3 * Hp;
     __hip_bfloat16* out_b = out + (long)b0 * out_row + (long)dir * Hp;
@@ -1245,7 +1250,8 @@ void gru_fwd_b1_kernel(const __hip_bfloat16* __restrict__ gi,
     float* bhh_s = (float*)p;
     auto hring = [&](int s) { return s ? hr1 : hr0; };
 
-    // stage the whole gi sequence (batch row 0, this direction)
+    // stage the whole gi sequence (batch row 0, this direction); with a
+    // single batch row the kernel needs no gi batch pitch
     const __hip_bfloat16* gi_b = gi + (long)dir * 3 * Hp;
     const long gi_trow = (long)n_dir * 3 * Hp;
     for (int idx = tid; idx < Tseq * (3 * Hp / 8); idx += NT) {
@@ -1831,7 +1837,7 @@ void gru_fwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
                        int B, int Tseq, int n_dir, int GB,
                        __hip_bfloat16* __restrict__ out_drop,
                        unsigned int drop_thr, float drop_scale,
-                       unsigned long long drop_seed) {
+                       unsigned long long drop_seed, long gi_pitch) {
     constexpr int CT = Hp / CS;          // column-blocks per group
     constexpr int NW = NT / 64;          // waves
     constexpr int MT = BR / 16 / NW;     // m-tiles per wave
@@ -1872,7 +1878,7 @@ void gru_fwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
     p += 2 * BR * GP;
     float* bhh_s = (float*)p;
 
-    const long gi_row = (long)Tseq * n_dir * 3 * Hp;
+    const long gi_row = gi_pitch;   // elements between batch rows of gi
     const long out_row = (long)Tseq * n_dir * Hp;
     // this block's gate rows: dir block, gate gslices at ct*CS
     const __hip_bfloat16* wdir = w + (long)dir * 3 * Hp * Hp;
@@ -2113,7 +2119,7 @@ extern "C" int fmda_gru_fwd_cs_launch(const void* gi, const void* w,
                                       unsigned int drop_thr,
                                       float drop_scale,
                                       unsigned long long drop_seed,
-                                      hipStream_t stream) {
+                                      long gi_pitch, hipStream_t stream) {
     constexpr int BR = 256, Hp = 512, CS = 32, NT = 512;
     const int GB = (B + BR - 1) / BR;
     const size_t lds = 2 * 3 * CS * (Hp + 8) + 2 * (size_t)BR * 3 * CS +
@@ -2127,7 +2133,7 @@ extern "C" int fmda_gru_fwd_cs_launch(const void* gi, const void* w,
                                  (__hip_bfloat16*)out, hlast,
                                  (__hip_bfloat16*)hpub, cnt, B, Tseq, n_dir,
                                  GB, (__hip_bfloat16*)out_drop, drop_thr,
-                                 drop_scale, drop_seed);
+                                 drop_scale, drop_seed, gi_pitch);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -3294,13 +3300,14 @@ static inline size_t bwd_lds_bytes(bool bf16, int Hp, int bt, bool wlds) {
 template <typename T, int BT, int Hp, bool WLDS, int NT, bool HOIST>
 static int launch_fwd(const void* gi, const void* w, const float* bhh,
                       void* out, float* hlast, int B, int Tseq, int n_dir,
-                      const float* h0, size_t lds, hipStream_t stream) {
+                      const float* h0, long gi_pitch, size_t lds,
+                      hipStream_t stream) {
     auto k = gru_fwd_kernel<T, BT, Hp, WLDS, NT, HOIST>;
     (void)hipFuncSetAttribute((const void*)k,
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const dim3 grid((B + BT - 1) / BT, n_dir);
     k<<<grid, NT, lds, stream>>>((const T*)gi, (const T*)w, bhh, (T*)out,
-                                 hlast, B, Tseq, n_dir, h0);
+                                 hlast, B, Tseq, n_dir, h0, gi_pitch);
     return 0;
 }
 
@@ -3329,7 +3336,7 @@ static int launch_fwd_v3_128(const void* gi, const void* w, const float* bhh,
                              void* out, float* hlast, int B, int Tseq,
                              int n_dir, const float* h0, void* out_drop,
                              unsigned int drop_thr, float drop_scale,
-                             unsigned long long drop_seed,
+                             unsigned long long drop_seed, long gi_pitch,
                              hipStream_t stream) {
     static const bool big = getenv("FMDA_FWD_BT32") != nullptr;
     if (big) {   // A/B: one 8-wave block per CU instead of two 4-wave
@@ -3344,7 +3351,8 @@ static int launch_fwd_v3_128(const void* gi, const void* w, const float* bhh,
                                       (const __hip_bfloat16*)w, bhh,
                                       (__hip_bfloat16*)out, hlast, B, Tseq,
                                       n_dir, h0, (__hip_bfloat16*)out_drop,
-                                      drop_thr, drop_scale, drop_seed);
+                                      drop_thr, drop_scale, drop_seed,
+                                      gi_pitch);
         return 0;
     }
     constexpr int BT = 16, Hp = 128, NT = 256;
@@ -3360,7 +3368,8 @@ static int launch_fwd_v3_128(const void* gi, const void* w, const float* bhh,
                                       (const __hip_bfloat16*)w, bhh,
                                       (__hip_bfloat16*)out, hlast, B, Tseq,
                                       n_dir, h0, (__hip_bfloat16*)out_drop,
-                                      drop_thr, drop_scale, drop_seed);
+                                      drop_thr, drop_scale, drop_seed,
+                                      gi_pitch);
         return 0;
     }
     if (pm && atoi(pm) == 1) {   // GEMM only, no gates
@@ -3372,7 +3381,8 @@ static int launch_fwd_v3_128(const void* gi, const void* w, const float* bhh,
                                       (const __hip_bfloat16*)w, bhh,
                                       (__hip_bfloat16*)out, hlast, B, Tseq,
                                       n_dir, h0, (__hip_bfloat16*)out_drop,
-                                      drop_thr, drop_scale, drop_seed);
+                                      drop_thr, drop_scale, drop_seed,
+                                      gi_pitch);
         return 0;
     }
     auto k = gru_fwd_v3_kernel<BT, Hp, NT, 2>;
@@ -3383,7 +3393,7 @@ static int launch_fwd_v3_128(const void* gi, const void* w, const float* bhh,
                                  (const __hip_bfloat16*)w, bhh,
                                  (__hip_bfloat16*)out, hlast, B, Tseq, n_dir,
                                  h0, (__hip_bfloat16*)out_drop, drop_thr,
-                                 drop_scale, drop_seed);
+                                 drop_scale, drop_seed, gi_pitch);
     return 0;
 }
 
@@ -3496,7 +3506,7 @@ extern "C" int fmda_gru_fwd_launch(int is_bf16, int Hp, const void* gi,
                                    const float* h0, void* out_drop,
                                    unsigned int drop_thr, float drop_scale,
                                    unsigned long long drop_seed,
-                                   hipStream_t stream) {
+                                   long gi_pitch, hipStream_t stream) {
     if (out_drop != nullptr && !(is_bf16 && Hp == 128))
         return -6;   // fused fwd dropout only on the bf16 Hp=128 path
     const LaunchCfg c = fwd_cfg(is_bf16, Hp);
@@ -3504,7 +3514,7 @@ extern "C" int fmda_gru_fwd_launch(int is_bf16, int Hp, const void* gi,
     if (lds > 160 * 1024) return -2;
 #define F(TY, BTV, HPV, WL, NTV, HO)                                           \
     launch_fwd<TY, BTV, HPV, WL, NTV, HO>(gi, w, bhh, out, hlast, B, Tseq,     \
-                                          n_dir, h0, lds, stream)
+                                          n_dir, h0, gi_pitch, lds, stream)
     if (is_bf16) {
         switch (Hp) {
             case 16: return -7;   // KK = Hp/32 = 0: zero-trip MFMA loop
@@ -3517,7 +3527,7 @@ extern "C" int fmda_gru_fwd_launch(int is_bf16, int Hp, const void* gi,
                     break;   // LDS-resident batch-1 kernel took it
                 launch_fwd_v3_128(gi, w, bhh, out, hlast, B, Tseq, n_dir,
                                   h0, out_drop, drop_thr, drop_scale,
-                                  drop_seed, stream);
+                                  drop_seed, gi_pitch, stream);
                 break;
             case 256: F(bf16_t, 32, 256, false, 512, false); break;
             case 512: F(bf16_t, 16, 512, false, 512, false); break;

@@ -530,6 +530,38 @@ def _packed_inference_weights(gru_module, layer, params, Hp, H, dtype):
     return packed
 
 
+def _layer_params(gru_module, layer: int, D: int):
+    """Per direction (w_ih, w_hh, b_ih, b_hh) masters of one nn.GRU layer."""
+    params = []
+    for sfx_d in ["", "_reverse"][:D]:
+        sfx = f"l{layer}{sfx_d}"
+        params.append((getattr(gru_module, f"weight_ih_{sfx}"),
+                       getattr(gru_module, f"weight_hh_{sfx}"),
+                       getattr(gru_module, f"bias_ih_{sfx}"),
+                       getattr(gru_module, f"bias_hh_{sfx}")))
+    return params
+
+
+def _unpad_out(out_pad: torch.Tensor, H: int, Hp: int, D: int):
+    """(B, T, D*Hp) kernel output -> (B, T, D*H)."""
+    if Hp == H:
+        return out_pad
+    if D == 2:
+        return torch.cat([out_pad[..., :H], out_pad[..., Hp:Hp + H]], dim=-1)
+    return out_pad[..., :H]
+
+
+def _infer_layer(gru_module, layer, params, Hp, H, inp, h0=None):
+    """Inference fast path of one layer: cached packed weights, one
+    projection GEMM, direct kernel call. Returns (out_pad, h_last)."""
+    w_ih_cat, b_ih_cat, w_hh_cat, b_hh_cat = _packed_inference_weights(
+        gru_module, layer, params, Hp, H, inp.dtype)
+    B, T, F = inp.shape
+    gi = torch.addmm(b_ih_cat, inp.reshape(B * T, F),
+                     w_ih_cat.t()).view(B, T, -1)
+    return load_extension().gru_fwd(gi, w_hh_cat, b_hh_cat, h0)
+
+
 def bigru_stack(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
                 bidirectional: bool, dropout_p: float, training: bool,
                 hidden: Optional[torch.Tensor] = None
@@ -559,13 +591,7 @@ def bigru_stack(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
     h_n_parts: List[torch.Tensor] = []
     inp = x
     for layer in range(n_layers):
-        p = {}
-        for d, sfx_d in enumerate(["", "_reverse"][:D]):
-            sfx = f"l{layer}{sfx_d}"
-            p[d] = (getattr(gru_module, f"weight_ih_{sfx}"),
-                    getattr(gru_module, f"weight_hh_{sfx}"),
-                    getattr(gru_module, f"bias_ih_{sfx}"),
-                    getattr(gru_module, f"bias_hh_{sfx}"))
+        p = _layer_params(gru_module, layer, D)
         # inter-layer dropout planned for this layer's output? choose the
         # seed NOW so the producing layer's BPTT kernel can apply the same
         # counter-based mask at its d_out read (backward pass fused away)
@@ -584,14 +610,8 @@ def bigru_stack(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
         h0_l = h0_layers[layer]
         dropped_pad = None
         if not training and not torch.is_grad_enabled():
-            # inference fast path: cached packed weights, direct kernel call
-            ext = load_extension()
-            w_ih_cat, b_ih_cat, w_hh_cat, b_hh_cat = _packed_inference_weights(
-                gru_module, layer, [p[d] for d in range(D)], Hp, H, x.dtype)
-            B, T, F = inp.shape
-            gi = torch.addmm(b_ih_cat, inp.reshape(B * T, F),
-                             w_ih_cat.t()).view(B, T, -1)
-            out_pad, h_last = ext.gru_fwd(gi, w_hh_cat, b_hh_cat, h0_l)
+            out_pad, h_last = _infer_layer(gru_module, layer, p, Hp, H, inp,
+                                           h0_l)
         elif D == 2:
             res = _BiGRULayer.apply(inp, Hp, *p[0], *p[1], *dp, h0_l)
             out_pad, h_last = res[0], res[1]
@@ -602,13 +622,7 @@ def bigru_stack(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
             out_pad, h_last = res[0], res[1]
             dropped_pad = res[2] if len(res) > 2 else None
 
-        if Hp == H:
-            out = out_pad
-        elif D == 2:
-            out = torch.cat([out_pad[..., :H], out_pad[..., Hp:Hp + H]],
-                            dim=-1)
-        else:
-            out = out_pad[..., :H]
+        out = _unpad_out(out_pad, H, Hp, D)
         h_n_parts.append(h_last[:, :, :H].to(x.dtype))
 
         inp = out
@@ -621,3 +635,57 @@ def bigru_stack(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
 
     h_n = torch.cat(h_n_parts, dim=0)  # (L*D, B, H)
     return inp, h_n
+
+
+def table_projections(table: torch.Tensor, gru_module: torch.nn.GRU,
+                      bidirectional: bool) -> torch.Tensor:
+    """Layer-0 input projections of every table row, once: gi_rows
+    (N, D*3Hp) = table @ W_ih^T + b_ih. A row's projection does not depend
+    on the window it sits in (eval mode: no input dropout), so every
+    sliding window over the table reads these rows in place."""
+    assert not torch.is_grad_enabled(), "windowed inference runs under no_grad"
+    enable_tunableop()
+    D = 2 if bidirectional else 1
+    H = gru_module.hidden_size
+    Hp = _pad_h(H)
+    w_ih_cat, b_ih_cat, _, _ = _packed_inference_weights(
+        gru_module, 0, _layer_params(gru_module, 0, D), Hp, H, table.dtype)
+    return torch.addmm(b_ih_cat, table, w_ih_cat.t())
+
+
+def bigru_stack_windows(table: torch.Tensor, gru_module: torch.nn.GRU,
+                        n_layers: int, bidirectional: bool, window: int,
+                        stride: int = 1,
+                        gi_rows: Optional[torch.Tensor] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bigru_stack (inference, zero h0) over every sliding window of a
+    normalised (N, F) table, without materialising the windows: window b is
+    table[b*stride : b*stride + window]. Layer 0 runs the recurrence
+    straight on the shared table of projections (gru_fwd_windows); layers
+    above take the ordinary inference path, their inputs differ per window.
+    gi_rows: table_projections of these table rows if the caller already
+    has them (a chunked caller computes them once for the whole table and
+    passes matching row-slices). Returns (out (B, window, D*H),
+    h_n (L*D, B, H)) like bigru_stack."""
+    assert not torch.is_grad_enabled(), "windowed inference runs under no_grad"
+    enable_tunableop()
+    D = 2 if bidirectional else 1
+    H = gru_module.hidden_size
+    Hp = _pad_h(H)
+    if gi_rows is None:
+        gi_rows = table_projections(table, gru_module, bidirectional)
+    assert gi_rows.shape[0] == table.shape[0], "gi_rows / table rows differ"
+    h_n_parts: List[torch.Tensor] = []
+    inp = None
+    for layer in range(n_layers):
+        p = _layer_params(gru_module, layer, D)
+        if layer == 0:
+            _, _, w_hh_cat, b_hh_cat = _packed_inference_weights(
+                gru_module, 0, p, Hp, H, gi_rows.dtype)
+            out_pad, h_last = load_extension().gru_fwd_windows(
+                gi_rows, w_hh_cat, b_hh_cat, window, stride)
+        else:
+            out_pad, h_last = _infer_layer(gru_module, layer, p, Hp, H, inp)
+        inp = _unpad_out(out_pad, H, Hp, D)
+        h_n_parts.append(h_last[:, :, :H].to(gi_rows.dtype))
+    return inp, torch.cat(h_n_parts, dim=0)

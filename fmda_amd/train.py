@@ -52,6 +52,41 @@ def chunk_batches(market, chunk_set, dcfg, batch_size):
             yield x, y
 
 
+def evaluate_chunks_windowed(model, market, chunk_set, dcfg, batch_size):
+    """model.evaluate_model(chunk_batches(...)) without materialised
+    windows: each chunk goes through BiGRU.window_batch_metrics as one
+    normalised table, with chunk_batches' batching (groups of `batch_size`
+    consecutive windows that never span two chunks), and the per-batch
+    metrics are averaged over all chunks. On the GPU the raw chunk is
+    normalised there by the normalize_table kernel."""
+    import numpy as np
+    X = market.X[:, :dcfg.n_features]
+    accs, hams, fbetas = [], [], []
+    pred_total, target_total = torch.LongTensor(), torch.LongTensor()
+    for indices, norms in chunk_set:
+        if model.device.type == "cuda":
+            from .ops import load_extension
+            ids = torch.tensor(list(indices), dtype=torch.long) - 1
+            dev = model.device
+            table = load_extension().normalize_table(
+                X[ids].float().contiguous().to(dev),
+                norms[0][0].float().contiguous().to(dev),
+                norms[1][0].float().contiguous().to(dev), torch.float32)
+            targets = torch.nan_to_num(market.Y[ids], nan=0.0)
+        else:
+            bl = BatchLoader(indices, norms, X, market.Y, dcfg.window)
+            table, targets = bl.x, bl.y
+        a, h, f, pred, target = model.window_batch_metrics(
+            table, targets, dcfg.window, batch_size)
+        accs += a
+        hams += h
+        fbetas += f
+        pred_total = torch.cat([pred_total, pred], dim=0)
+        target_total = torch.cat([target_total, target], dim=0)
+    return (np.mean(accs), np.mean(hams), np.mean(fbetas, axis=0),
+            pred_total, target_total)
+
+
 def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
           tcfg: TrainConfig = None, checkpoint_path: str = "model_params.pt",
           norm_params_path: str = "norm_params", log=print,
@@ -110,6 +145,13 @@ def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
             start_epoch = ts["epoch"] + 1
             torch.set_rng_state(ts["rng"])
 
+    def evaluate(chunk_set):
+        if tcfg.windowed_eval:
+            return evaluate_chunks_windowed(model, market, chunk_set, dcfg,
+                                            tcfg.batch_size)
+        return model.evaluate_model(
+            chunk_batches(market, chunk_set, dcfg, tcfg.batch_size))
+
     history = []
     best_val_acc = -1.0
     for epoch in range(start_epoch, tcfg.epochs + 1):
@@ -118,8 +160,7 @@ def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
                                                 norm_params_path)
         tr = model.train_model(
             chunk_batches(market, train_set, dcfg, tcfg.batch_size))
-        va = model.evaluate_model(
-            chunk_batches(market, val_set, dcfg, tcfg.batch_size))
+        va = evaluate(val_set)
         from .metrics import three_class_accuracy
         rec = {"epoch": epoch, "train_acc": float(tr[0]),
                "train_hamming": float(tr[1]), "train_loss": float(tr[2]),
@@ -147,8 +188,7 @@ def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
     # (reference notebook cells 33-37).
     from .metrics import multilabel_confusion, three_class_accuracy
     _, _, test_set = make_epoch_sets(market, dcfg, norm_params_path)
-    te = model.evaluate_model(
-        chunk_batches(market, test_set, dcfg, tcfg.batch_size))
+    te = evaluate(test_set)
     import math
 
     import numpy as np
@@ -183,6 +223,9 @@ def main():
     ap.add_argument("--window", type=int, default=30)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--device", default="cpu")
+    ap.add_argument("--windowed-eval", action="store_true",
+                    help="validate / test each chunk as one table through "
+                         "BiGRU.evaluate_windows (no materialised windows)")
     ap.add_argument("--checkpoint", default="model_params.pt")
     ap.add_argument("--resume", default=None,
                     help="checkpoint to resume from (model_params.pt format)")
@@ -196,7 +239,8 @@ def main():
                        spatial_dropout=False, dropout=0.5)
     dcfg = DataConfig(n_rows=args.rows, window=args.window)
     tcfg = TrainConfig(batch_size=args.batch, epochs=args.epochs,
-                       device=args.device)
+                       device=args.device,
+                       windowed_eval=args.windowed_eval)
     if args.log_file:
         fh = open(args.log_file, "a")
 
