@@ -47,8 +47,18 @@ extern "C" int fmda_mfma_selftest_launch(const void* A, const void* Bm,
                                          float* C, hipStream_t stream);
 extern "C" int fmda_pool_fwd_launch(int is_bf16, const void* out, void* maxv,
                                     void* avgv, int* amax, int B, int Tseq,
-                                    int H, int n_dir, int act_io,
+                                    int H, int n_dir, int act_io, int serial,
                                     hipStream_t stream);
+extern "C" int fmda_pool_features_fwd_launch(const void* out,
+                                             const float* hlast, void* feat,
+                                             int* amax, int B, int Tseq,
+                                             int H, int n_dir,
+                                             hipStream_t stream);
+extern "C" int fmda_pool_features_bwd_launch(const void* dfeat,
+                                             const int* amax, void* dout,
+                                             float* dhlast, int B, int Tseq,
+                                             int H, int n_dir, long ld,
+                                             hipStream_t stream);
 extern "C" int fmda_pool_bwd_launch(int is_bf16, const void* dmax,
                                     const void* davg, const int* amax,
                                     void* dout, int B, int Tseq, int H,
@@ -347,8 +357,15 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
     const bool column_split = is_bf16 && Hp == 512 && h0 == nullptr;
     const int64_t db_rows = fmda_gru_bwd_db_rows(is_bf16 ? 1 : 0, Hp, B,
                                                  column_split ? 1 : 0);
-    auto dbpart = torch::zeros({db_rows, n_dir, 4 * Hp},
-                               gi.options().dtype(torch::kFloat32));
+    // The batch-parallel kernels (gru_bwd_kernel, gru_bwd_v3_kernel) run a
+    // (batch tile, dir) grid, and every block's epilogue stores all 4 slots
+    // of all Hp / 16 column tiles of its row (the tiles are dealt out
+    // ct = wave + NW * i over all NW waves), so the table needs no fill.
+    // The column-split kernel's rows keep their zero fill.
+    auto dbopts = gi.options().dtype(torch::kFloat32);
+    auto dbpart = column_split
+        ? torch::zeros({db_rows, n_dir, 4 * Hp}, dbopts)
+        : torch::empty({db_rows, n_dir, 4 * Hp}, dbopts);
     // W^T for the carry GEMM's B fragments (v3 kernel streams them from
     // L2 as contiguous bf16x8 rows instead of hoisting 48 VGPRs). A caller
     // that packed the weights with pack_gru_layer already has it.
@@ -436,8 +453,10 @@ torch::Tensor mfma_selftest(torch::Tensor A, torch::Tensor Bm) {
 
 // act_dtype: return max / avg in out's dtype instead of fp32 (the kernel
 // rounds where the caller's .to(out.dtype) would have).
+// serial: always a thread-per-column kernel (T summed in ascending order),
+// also for the small grids that by default get the wave-per-pair kernel.
 std::vector<torch::Tensor> pool_fwd(torch::Tensor out, int64_t n_dir,
-                                    bool act_dtype) {
+                                    bool act_dtype, bool serial) {
     TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 3);
     const bool bf16 = out.scalar_type() == torch::kBFloat16;
     TORCH_CHECK(bf16 || out.scalar_type() == torch::kFloat32);
@@ -455,9 +474,76 @@ std::vector<torch::Tensor> pool_fwd(torch::Tensor out, int64_t n_dir,
     int rc = fmda_pool_fwd_launch(bf16 ? 1 : 0, out.data_ptr(),
                                   maxv.data_ptr(), avgv.data_ptr(),
                                   amax.data_ptr<int>(), B, T, H, (int)n_dir,
-                                  act_io ? 1 : 0, stream.stream());
+                                  act_io ? 1 : 0, serial ? 1 : 0,
+                                  stream.stream());
     TORCH_CHECK(rc == 0, "pool_fwd launch failed");
     return {maxv, avgv, amax};
+}
+
+// Pooled-head features in one kernel: out (B, T, D*H) bf16 and the raw
+// h_last (D, B, H) fp32 of the top layer -> feat (B, 3H) bf16 =
+// [dirsum(h_last) | max_T | avg_T] and amax (B, H) int32. The same bits as
+// pool_fwd(act_dtype, serial) plus the eager h_n cast / direction sum / cat.
+std::vector<torch::Tensor> pool_features_fwd(torch::Tensor out,
+                                             torch::Tensor hlast) {
+    TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 3 &&
+                out.scalar_type() == torch::kBFloat16,
+                "pool_features_fwd: out must be contiguous bf16 (B, T, D*H) "
+                "on the GPU");
+    TORCH_CHECK(hlast.is_cuda() && hlast.is_contiguous() &&
+                hlast.dim() == 3 && hlast.scalar_type() == torch::kFloat32,
+                "pool_features_fwd: h_last must be contiguous fp32 (D, B, H)");
+    const int64_t B = out.size(0), T = out.size(1);
+    const int64_t D = hlast.size(0), H = hlast.size(2);
+    TORCH_CHECK((D == 1 || D == 2) && hlast.size(1) == B &&
+                out.size(2) == D * H, "pool_features_fwd: shape mismatch");
+    TORCH_CHECK(H % 8 == 0 && H >= 8 && T >= 1 && B >= 1,
+                "pool_features_fwd: needs H % 8 == 0 and a non-empty input");
+    TORCH_CHECK(T <= INT_MAX && B * (H / 8) <= INT_MAX - 256,
+                "pool_features_fwd: too large");
+    auto feat = torch::empty({B, 3 * H}, out.options());
+    auto amax = torch::empty({B, H}, out.options().dtype(torch::kInt32));
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_pool_features_fwd_launch(
+        out.data_ptr(), hlast.data_ptr<float>(), feat.data_ptr(),
+        amax.data_ptr<int>(), (int)B, (int)T, (int)H, (int)D,
+        stream.stream());
+    TORCH_CHECK(rc == 0, "pool_features_fwd launch failed rc=", rc);
+    return {feat, amax};
+}
+
+// Backward of pool_features_fwd in one kernel: dfeat (B, 3H) bf16, rows
+// possibly pitched -> d_out (B, T, D*H) bf16 as pool_bwd writes it, and
+// d_hlast (D, B, H) fp32 = float(dfeat[:, :H]) for every direction.
+std::vector<torch::Tensor> pool_features_bwd(torch::Tensor dfeat,
+                                             torch::Tensor amax, int64_t T,
+                                             int64_t n_dir) {
+    TORCH_CHECK(dfeat.is_cuda() && dfeat.dim() == 2 &&
+                dfeat.scalar_type() == torch::kBFloat16 &&
+                amax.is_cuda() && amax.is_contiguous() && amax.dim() == 2 &&
+                amax.scalar_type() == torch::kInt32,
+                "pool_features_bwd: dfeat must be bf16 (B, 3H), amax "
+                "contiguous int32 (B, H), both on the GPU");
+    const int64_t B = amax.size(0), H = amax.size(1);
+    TORCH_CHECK(dfeat.size(0) == B && dfeat.size(1) == 3 * H,
+                "pool_features_bwd: shape mismatch");
+    TORCH_CHECK(dfeat.stride(1) == 1 &&
+                (B == 1 || dfeat.stride(0) >= 3 * H),
+                "pool_features_bwd: dfeat needs unit column stride");
+    TORCH_CHECK((n_dir == 1 || n_dir == 2) && H % 8 == 0 && H >= 8 &&
+                T >= 1 && B >= 1 && T <= INT_MAX &&
+                B * (H / 8) <= INT_MAX - 256,
+                "pool_features_bwd: unsupported shape");
+    auto dout = torch::empty({B, T, n_dir * H}, dfeat.options());
+    auto dhlast = torch::empty({n_dir, B, H},
+                               dfeat.options().dtype(torch::kFloat32));
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_pool_features_bwd_launch(
+        dfeat.data_ptr(), amax.data_ptr<int>(), dout.data_ptr(),
+        dhlast.data_ptr<float>(), (int)B, (int)T, (int)H, (int)n_dir,
+        B == 1 ? 3 * H : (long)dfeat.stride(0), stream.stream());
+    TORCH_CHECK(rc == 0, "pool_features_bwd launch failed rc=", rc);
+    return {dout, dhlast};
 }
 
 torch::Tensor pool_bwd(torch::Tensor dmax, torch::Tensor davg,
@@ -880,7 +966,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("head_sigmoid", &head_sigmoid,
           "linear head + sigmoid emitting probabilities");
     m.def("pool_fwd", &pool_fwd, "fused dirsum+max/avg pooling forward",
-          py::arg("out"), py::arg("n_dir"), py::arg("act_dtype") = false);
+          py::arg("out"), py::arg("n_dir"), py::arg("act_dtype") = false,
+          py::arg("serial") = false);
+    m.def("pool_features_fwd", &pool_features_fwd,
+          "[dirsum(h_last) | max | avg] features + argmax in one kernel",
+          py::arg("out"), py::arg("h_last"));
+    m.def("pool_features_bwd", &pool_features_bwd,
+          "d_out and d_hlast of pool_features_fwd in one kernel",
+          py::arg("dfeat"), py::arg("amax"), py::arg("T"), py::arg("n_dir"));
     m.def("pool_bwd", &pool_bwd, "fused pooling backward (d_out assembly)");
     m.def("head_loss_fwd", &head_loss_fwd, "fused head GEMM + BCE loss");
     m.def("head_loss_bwd", &head_loss_bwd, "fused head/loss backward");

@@ -2852,14 +2852,16 @@ __global__ void pool_fwd_small_kernel(const T* __restrict__ out,
 }
 
 // act_io != 0 (bf16 only): maxv / avgv are bf16 like the activations.
+// serial != 0: never the small-grid kernel, whose lanes split T and sum it
+// in another order than the thread-per-column kernels' ascending t.
 extern "C" int fmda_pool_fwd_launch(int is_bf16, const void* out, void* maxv,
                                     void* avgv, int* amax, int B, int Tseq,
-                                    int H, int n_dir, int act_io,
+                                    int H, int n_dir, int act_io, int serial,
                                     hipStream_t stream) {
     using bf16 = __hip_bfloat16;
     if (act_io && !is_bf16) return -2;
     const int n = B * (H / 2);   // thread per h-pair (H is always even)
-    if (n < 4096) {
+    if (n < 4096 && !serial) {
         // small grid (streaming predict): wave per pair, lanes over T
         const dim3 grid((n + 3) / 4);
         if (act_io)
@@ -2941,6 +2943,182 @@ extern "C" int fmda_pool_bwd_launch(int is_bf16, const void* dmax,
         pool_bwd_kernel<float, float><<<grid, 256, 0, stream>>>(
             (const float*)dmax, (const float*)davg, amax, (float*)dout, B,
             Tseq, H, n_dir, ld_max, ld_avg);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ===========================================================================
+// Pooled-head feature path in two kernels (bf16, H % 8 == 0, unpadded H):
+// feat (B, 3H) = [dirsum(h_last) | max_T | avg_T] straight from the top
+// layer's out and raw fp32 h_last, and its backward. Every value is what
+// pool_fwd_oct_kernel / pool_bwd_oct_kernel plus the eager cast / sum / cat
+// chain around them produce, bit for bit:
+// - max / avg / amax: pool_fwd_oct_kernel's arithmetic in its order (fp32
+//   direction sum, s += x in ascending t, first strictly greater value
+//   wins, one rounding of s / T);
+// - last hidden: each direction's fp32 h_last rounded to bf16 (the h_n
+//   cast), the two added in fp32 and rounded again (torch's bf16 sum over
+//   the direction axis accumulates in fp32); one direction: the first
+//   rounding alone.
+// ===========================================================================
+FMDA_DEV void pool_oct_consume(const bf16x8_t& v, const bf16x8_t& w,
+                               bool two_dir, int t, float (&mx)[8],
+                               float (&s)[8], int (&im)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float x = (float)((const __bf16*)&v)[k];
+        if (two_dir) x += (float)((const __bf16*)&w)[k];
+        s[k] += x;
+        if (x > mx[k]) { mx[k] = x; im[k] = t; }
+    }
+}
+
+// One thread per (b, 8-column group) like pool_fwd_oct_kernel, which ran
+// at 4.2 TB/s with one or two 16-byte loads in flight per thread and only
+// 8 waves per CU: here the loads of UNR consecutive timesteps are issued
+// before the first is consumed (UNR * ND * 16 bytes in flight per thread);
+// the timesteps are still consumed in ascending order.
+template <int ND, int UNR>
+__global__ __launch_bounds__(256) void pool_features_fwd_kernel(
+        const __hip_bfloat16* __restrict__ out,
+        const float* __restrict__ hlast, __hip_bfloat16* __restrict__ feat,
+        int* __restrict__ amax, int B, int Tseq, int H) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int H8 = H / 8;
+    if (idx >= B * H8) return;
+    const int b = idx / H8;
+    const int h8 = (idx % H8) * 8;
+    const int HD = ND * H;
+    const __hip_bfloat16* p = out + (long)b * Tseq * HD + h8;
+    float mx[8], s[8];
+    int im[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { mx[k] = -3.4e38f; s[k] = 0.0f; im[k] = 0; }
+    int t = 0;
+    for (; t + UNR <= Tseq; t += UNR) {
+        bf16x8_t v[UNR], w[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const __hip_bfloat16* pt = p + (long)(t + u) * HD;
+            v[u] = *(const bf16x8_t*)pt;
+            if (ND == 2) w[u] = *(const bf16x8_t*)(pt + H);
+            else w[u] = v[u];
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u)
+            pool_oct_consume(v[u], w[u], ND == 2, t + u, mx, s, im);
+    }
+    for (; t < Tseq; ++t) {
+        const __hip_bfloat16* pt = p + (long)t * HD;
+        const bf16x8_t v = *(const bf16x8_t*)pt;
+        bf16x8_t w = v;
+        if (ND == 2) w = *(const bf16x8_t*)(pt + H);
+        pool_oct_consume(v, w, ND == 2, t, mx, s, im);
+    }
+
+    const float* h0p = hlast + (long)b * H + h8;
+    bf16x8_t fl, fm, fa;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        __hip_bfloat16 l = __float2bfloat16(h0p[k]);
+        if (ND == 2) {
+            const __hip_bfloat16 r = __float2bfloat16(h0p[(long)B * H + k]);
+            l = __float2bfloat16(__bfloat162float(l) + __bfloat162float(r));
+        }
+        ((__hip_bfloat16*)&fl)[k] = l;
+        ((__hip_bfloat16*)&fm)[k] = from_f32<__hip_bfloat16>(mx[k]);
+        ((__hip_bfloat16*)&fa)[k] =
+            from_f32<__hip_bfloat16>(s[k] / (float)Tseq);
+    }
+    __hip_bfloat16* fr = feat + (long)b * 3 * H + h8;
+    *(bf16x8_t*)fr = fl;
+    *(bf16x8_t*)(fr + H) = fm;
+    *(bf16x8_t*)(fr + 2 * H) = fa;
+    int* ao = amax + (long)b * H + h8;   // 32-byte aligned: H % 8 == 0
+    *(int4*)ao = make_int4(im[0], im[1], im[2], im[3]);
+    *(int4*)(ao + 4) = make_int4(im[4], im[5], im[6], im[7]);
+}
+
+// Backward of the whole feature path from dfeat (B, 3H) with row pitch ld
+// (elements): d_out (B, T, ND*H) exactly as pool_bwd_oct_kernel assembles
+// it from the max / avg column blocks, and d_hlast (ND, B, H) fp32 =
+// float(dfeat[:, :H]) for every direction (what the sum / cat / cast chain
+// hands back to the top layer).
+template <int ND>
+__global__ __launch_bounds__(256) void pool_features_bwd_kernel(
+        const __hip_bfloat16* __restrict__ dfeat,
+        const int* __restrict__ amax, __hip_bfloat16* __restrict__ dout,
+        float* __restrict__ dhlast, int B, int Tseq, int H, long ld) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int H8 = H / 8;
+    if (idx >= B * H8) return;
+    const int b = idx / H8;
+    const int h8 = (idx % H8) * 8;
+    const __hip_bfloat16* dr = dfeat + (long)b * ld + h8;
+    const int* ai = amax + (long)b * H + h8;
+    float* dh = dhlast + (long)b * H + h8;
+    float ga[8], gm[8], gl[8];
+    int im[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        gl[k] = __bfloat162float(dr[k]);
+        gm[k] = __bfloat162float(dr[H + k]);
+        ga[k] = __bfloat162float(dr[2 * H + k]) / (float)Tseq;
+        im[k] = ai[k];
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {   // 32-byte aligned: H % 8 == 0
+        float* dhd = dh + (long)d * B * H;
+        *(float4*)dhd = make_float4(gl[0], gl[1], gl[2], gl[3]);
+        *(float4*)(dhd + 4) = make_float4(gl[4], gl[5], gl[6], gl[7]);
+    }
+    const int HD = ND * H;
+    __hip_bfloat16* p = dout + (long)b * Tseq * HD + h8;
+    for (int t = 0; t < Tseq; ++t) {
+        bf16x8_t v;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            ((__bf16*)&v)[k] =
+                (__bf16)__float2bfloat16(ga[k] + (t == im[k] ? gm[k] : 0.0f));
+        *(bf16x8_t*)(p + (long)t * HD) = v;
+        if (ND == 2) *(bf16x8_t*)(p + (long)t * HD + H) = v;
+    }
+}
+
+extern "C" int fmda_pool_features_fwd_launch(const void* out,
+                                             const float* hlast, void* feat,
+                                             int* amax, int B, int Tseq,
+                                             int H, int n_dir,
+                                             hipStream_t stream) {
+    using bf16 = __hip_bfloat16;
+    if (H % 8 != 0 || (n_dir != 1 && n_dir != 2) || Tseq < 1) return -2;
+    const int n8 = B * (H / 8);
+    const dim3 grid((n8 + 255) / 256);
+    // load depth 8: measured at the flagship shape (B8192 T120 H128), depths
+    // 6, 8 and 15 all sit at 94-96 us (5.3 TB/s); 4 takes 113 us
+    if (n_dir == 2)
+        pool_features_fwd_kernel<2, 8><<<grid, 256, 0, stream>>>(
+            (const bf16*)out, hlast, (bf16*)feat, amax, B, Tseq, H);
+    else
+        pool_features_fwd_kernel<1, 8><<<grid, 256, 0, stream>>>(
+            (const bf16*)out, hlast, (bf16*)feat, amax, B, Tseq, H);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int fmda_pool_features_bwd_launch(const void* dfeat,
+                                             const int* amax, void* dout,
+                                             float* dhlast, int B, int Tseq,
+                                             int H, int n_dir, long ld,
+                                             hipStream_t stream) {
+    using bf16 = __hip_bfloat16;
+    if (H % 8 != 0 || (n_dir != 1 && n_dir != 2) || Tseq < 1) return -2;
+    const int n8 = B * (H / 8);
+    const dim3 grid((n8 + 255) / 256);
+    if (n_dir == 2)
+        pool_features_bwd_kernel<2><<<grid, 256, 0, stream>>>(
+            (const bf16*)dfeat, amax, (bf16*)dout, dhlast, B, Tseq, H, ld);
+    else
+        pool_features_bwd_kernel<1><<<grid, 256, 0, stream>>>(
+            (const bf16*)dfeat, amax, (bf16*)dout, dhlast, B, Tseq, H, ld);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

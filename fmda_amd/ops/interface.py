@@ -35,10 +35,11 @@ def _pad_h(H: int) -> int:
 
 def _glue_mode() -> int:
     """FMDA_NATIVE_GLUE, read per call:
-    1 (default): weight packing, the head's read of the fp32 masters and
-       the pooling casts run as single HIP kernels (csrc/glue_kernels.hip).
-       Every one of these steps is exact, so a training step computes what
-       the eager formulation computes, bit for bit.
+    1 (default): weight packing, the head's read of the fp32 masters, the
+       pooling casts and the pooled-head feature path (pooled_features) run
+       as single HIP kernels. Every one of these steps is exact, so a
+       training step computes what the eager formulation computes, bit for
+       bit.
     2: also the weight-gradient reductions (finalize_gru_wgrads,
        head_wgrads). They sum in fp32 in their own fixed order, and the
        head's dW / db skip the round trip through bf16, so gradients differ
@@ -291,6 +292,55 @@ class _DirSumPool(torch.autograd.Function):
 
 def dirsum_pool(out: torch.Tensor, n_dir: int):
     return _DirSumPool.apply(out, n_dir)
+
+
+class _PooledFeatures(torch.autograd.Function):
+    """(out (B, T, D*H) bf16, raw h_last (D, B, H) fp32) -> feat (B, 3H)
+    bf16 = [dirsum(h_last) | max_T | avg_T], one kernel each way. Forward
+    and backward give the bits of the chain they replace: the h_n cast,
+    hidden_v[-1].sum(0), dirsum_pool, torch.cat and their autograd
+    (d_hlast = float(dfeat[:, :H]) for every direction)."""
+
+    @staticmethod
+    def forward(ctx, out, h_last):
+        ext = load_extension()
+        feat, amax = ext.pool_features_fwd(out.contiguous(),
+                                           h_last.contiguous())
+        ctx.save_for_backward(amax)
+        ctx.meta = (out.shape[1], h_last.shape[0])
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        ext = load_extension()
+        (amax,) = ctx.saved_tensors
+        T, n_dir = ctx.meta
+        if (dfeat.dtype != torch.bfloat16 or dfeat.stride(1) != 1
+                or dfeat.stride(0) < dfeat.shape[1]):
+            dfeat = dfeat.to(torch.bfloat16).contiguous()
+        d_out, d_hlast = ext.pool_features_bwd(dfeat, amax, T, n_dir)
+        return d_out, d_hlast
+
+
+# fmda_pool_fwd_launch gives grids below this many column pairs to the
+# wave-per-pair kernel, which sums T in a lane-butterfly order
+_POOL_SMALL_GRID = 4096
+
+
+def pooled_features_native(x: torch.Tensor, H: int) -> bool:
+    """Whether the model input x (B, T, F) gets its pooled features from
+    pooled_features(out, raw h_last): bf16 on the GPU, whole 8-column
+    groups, unpadded H, native glue on, and a grid that dirsum_pool gives
+    to its thread-per-column kernel. Below that grid size (the batch-1
+    predict path) dirsum_pool sums T in another order, so the eager chain
+    stays and results stay what they were."""
+    return (_native_glue() and x.is_cuda and x.dtype == torch.bfloat16
+            and H % 8 == 0 and H <= _ALLOWED_HP[-1] and _pad_h(H) == H
+            and x.shape[0] * (H // 2) >= _POOL_SMALL_GRID)
+
+
+def pooled_features(out: torch.Tensor, h_last: torch.Tensor) -> torch.Tensor:
+    return _PooledFeatures.apply(out, h_last)
 
 
 class _HeadLoss(torch.autograd.Function):
@@ -573,6 +623,27 @@ def bigru_stack(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
     inside the single-layer autograd node. Replaces the reference's
     `self.gru(input_seq)` call (biGRU_model.py:102); `hidden` is the
     optional (L*D, B, H) initial state of the nn.GRU signature."""
+    out, h_n, _ = _bigru_stack(x, gru_module, n_layers, bidirectional,
+                               dropout_p, training, hidden)
+    return out, h_n
+
+
+def bigru_stack_raw(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
+                    bidirectional: bool, dropout_p: float, training: bool,
+                    hidden: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bigru_stack for a caller that wants only the top layer's state:
+    returns (out, h_last) with h_last the top layer's raw fp32 (D, B, Hp)
+    final state as the recurrence kernel left it. h_n is not assembled, so
+    the lower layers' final states cost no cast and no cat."""
+    out, _, h_last = _bigru_stack(x, gru_module, n_layers, bidirectional,
+                                  dropout_p, training, hidden, need_h_n=False)
+    return out, h_last
+
+
+def _bigru_stack(x, gru_module, n_layers, bidirectional, dropout_p, training,
+                 hidden=None, need_h_n=True):
+    """(out, h_n or None, raw fp32 h_last of the top layer)."""
     enable_tunableop()
     D = 2 if bidirectional else 1
     H = gru_module.hidden_size
@@ -623,7 +694,8 @@ def bigru_stack(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
             dropped_pad = res[2] if len(res) > 2 else None
 
         out = _unpad_out(out_pad, H, Hp, D)
-        h_n_parts.append(h_last[:, :, :H].to(x.dtype))
+        if need_h_n:
+            h_n_parts.append(h_last[:, :, :H].to(x.dtype))
 
         inp = out
         if drop_here:
@@ -633,8 +705,8 @@ def bigru_stack(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
             else:
                 inp = fused_dropout(inp, dropout_p)
 
-    h_n = torch.cat(h_n_parts, dim=0)  # (L*D, B, H)
-    return inp, h_n
+    h_n = torch.cat(h_n_parts, dim=0) if need_h_n else None  # (L*D, B, H)
+    return inp, h_n, h_last
 
 
 def table_projections(table: torch.Tensor, gru_module: torch.nn.GRU,
