@@ -94,6 +94,10 @@ class TrainConfig:
     # validate / test each chunk as one table (BiGRU.evaluate_windows):
     # layer-0 projections shared by overlapping windows, no DataLoader
     windowed_eval: bool = False
+    # train each chunk as one table kept on the device
+    # (BiGRU.train_windows): window gather + input dropout in one kernel,
+    # fused head+loss and FusedClipAdam on the GPU, tables in `dtype`
+    windowed_train: bool = False
 
 
 @dataclass

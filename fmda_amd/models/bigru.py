@@ -90,6 +90,12 @@ class BiGRU(nn.Module):
         """Everything before the linear head: returns the pooled concat
         (B, 3H) feature vector — the input of the reference's linear head
         (biGRU_model.py:133-137). Used by the fused head+loss kernel."""
+        return self._features_after_dropout(
+            self._input_dropout(input_seq), hidden)
+
+    def _input_dropout(self, input_seq: torch.Tensor) -> torch.Tensor:
+        """Input (spatial) dropout of forward_features
+        (biGRU_model.py:87-94)."""
         if self.spatial_dropout:
             if (self.training and input_seq.is_cuda
                     and input_seq.dtype == torch.bfloat16
@@ -109,7 +115,13 @@ class BiGRU(nn.Module):
             input_seq = fused_dropout(input_seq, self.dropout_p)
         else:
             input_seq = self.dropout(input_seq)
+        return input_seq
 
+    def _features_after_dropout(self, input_seq: torch.Tensor,
+                                hidden: Optional[torch.Tensor] = None
+                                ) -> torch.Tensor:
+        """forward_features from the already dropped input on: the GRU
+        stack and the pooled concat."""
         if input_seq.is_cuda:
             from ..ops.interface import (bigru_stack_raw, pooled_features,
                                          pooled_features_native)
@@ -259,6 +271,110 @@ class BiGRU(nn.Module):
     def add_device(self, device=torch.device('cpu')):
         """Specify the device (biGRU_model.py:155-159)."""
         self.device = device
+
+    def forward_features_windows(self, table: torch.Tensor,
+                                 starts: torch.Tensor,
+                                 window: int) -> torch.Tensor:
+        """forward_features of the batch of windows
+        table[starts[b] : starts[b] + window] of a normalised (N, F) table.
+        In training mode on the bf16 GPU path the batch is written already
+        dropped by one kernel (ops.interface.window_batch with this model's
+        dropout_p / spatial_dropout); the result equals
+        forward_features(table[starts[:, None] + arange(window)]) bit for
+        bit under the same RNG state. Every other case gathers and takes
+        forward_features' own input dropout. `starts`: int64, validated
+        here if it lives on the CPU, trusted if on the table's device."""
+        from ..ops.interface import window_batch
+        assert table.dim() == 2 and table.size(1) == self.n_features, \
+            f"table must be (N, {self.n_features})"
+        if (self.training and self.dropout_p > 0 and table.is_cuda
+                and table.dtype == torch.bfloat16):
+            x = window_batch(table, starts, window, p=self.dropout_p,
+                             spatial=self.spatial_dropout)
+        else:
+            x = self._input_dropout(window_batch(table, starts, window))
+        return self._features_after_dropout(x)
+
+    def _loss_weights(self):
+        """(weight, pos_weight) of the attached BCEWithLogitsLoss as the
+        fused head+loss kernel takes them (ones where the loss has none)."""
+        ones = None
+        out = []
+        for name in ("weight", "pos_weight"):
+            w = getattr(self.loss_fn, name, None)
+            if w is None:
+                if ones is None:
+                    ones = torch.ones(self.output_size, device=self.device)
+                w = ones
+            out.append(w)
+        return out
+
+    def train_windows(self, table: torch.Tensor, targets: torch.Tensor,
+                      window: int, batch_size: int, shuffle: bool = False):
+        """Train on the stride-1 windows of one normalised (N, F) table
+        that stays on the device: the training counterpart of
+        window_batch_metrics. Batches are groups of `batch_size`
+        consecutive windows (the last partial one is kept), as a sequential
+        DataLoader over the windows forms them; shuffle=True permutes the
+        windows first (torch.randperm on the CPU generator). The target of
+        a window is the targets row of its last timestep.
+
+        On the GPU a step is forward_features_windows -> fused_head_loss
+        (weights of self.loss_fn) -> backward -> optimizer, where a
+        FusedClipAdam clips by itself and any other optimizer is preceded
+        by clip_grad_norm_. On CPU a step is train_model's, on the
+        gathered windows. Returns the per-batch lists (accuracies, Hamming
+        losses, losses, fbetas); a table shorter than one window has no
+        batches. Losses and metrics stay on the device until the table is
+        done."""
+        from ..optim import FusedClipAdam
+        self.train()
+        if table.size(0) < window:
+            return [], [], [], []
+        table = table.to(self.device)
+        targets = targets.to(self.device)
+        n_windows = table.size(0) - window + 1
+        order = (torch.randperm(n_windows) if shuffle
+                 else torch.arange(n_windows))
+        # built here from [0, n_windows): valid by construction, so the
+        # per-batch slices go to window_batch as device tensors
+        order = order.to(self.device)
+        fused = table.is_cuda
+        if fused:
+            from ..ops.interface import fused_head_loss
+            wgt, pw = self._loss_weights()
+        losses, accs, hams, fbetas = [], [], [], []
+        for b0 in range(0, n_windows, batch_size):
+            starts = order[b0:b0 + batch_size]
+            target = targets[starts + (window - 1)]
+            self.optimizer.zero_grad()
+            if fused:
+                feats = self.forward_features_windows(table, starts, window)
+                loss, pred = fused_head_loss(feats, self.linear.weight,
+                                             self.linear.bias, target, wgt,
+                                             pw)
+            else:
+                idx = starts[:, None] + torch.arange(window)
+                pred = self.forward(table[idx])
+                loss = self.loss_fn(pred, target)
+            loss.backward()
+            losses.append(loss.detach())
+            if not isinstance(self.optimizer, FusedClipAdam):
+                nn.utils.clip_grad_norm_(self.parameters(), self.clip)
+            self.optimizer.step()
+
+            pred = torch.sigmoid(pred.detach()) > 0.5
+            acc, ham, fbeta = batch_metrics(target, pred, beta=0.5)
+            accs.append(acc)
+            hams.append(ham)
+            fbetas.append(fbeta)
+        # one transfer per table instead of three syncs per step
+        losses = torch.stack(losses).cpu().numpy()
+        accs = torch.stack(accs).cpu().numpy()
+        hams = torch.stack(hams).cpu().numpy()
+        fbetas = torch.stack(fbetas).cpu().numpy()
+        return ([float(a) for a in accs], [float(h) for h in hams],
+                list(losses), list(fbetas))
 
     def train_model(self, train_iterator):
         """One training epoch; returns (mean accuracy, mean Hamming loss,

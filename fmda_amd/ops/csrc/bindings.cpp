@@ -123,6 +123,10 @@ extern "C" int fmda_head_bwd_master_launch(
 extern "C" int fmda_normalize_table_launch(
         int out_bf16, const float* x, const float* xmin, const float* xmax,
         void* y, long N, int F, hipStream_t stream);
+extern "C" int fmda_window_batch_launch(
+        int is_bf16, const void* table, const long* starts, void* out,
+        long B, long Tlen, long F, int mode, unsigned int thr, float scale,
+        unsigned long long seed, hipStream_t stream);
 extern "C" int fmda_head_wgrads_slabs(int B);
 extern "C" int fmda_head_wgrads_launch(
         int is_bf16, const float* dlogits, const void* x, float* dw_part,
@@ -702,6 +706,51 @@ torch::Tensor normalize_table(torch::Tensor x, torch::Tensor x_min,
     return y;
 }
 
+// (B, window, F) batch of the windows table[starts[b] : starts[b] + window]
+// of a normalised (N, F) table, in the table's dtype, with input dropout
+// fused into the one write pass: for bf16 and p > 0 the result is bitwise
+// dropout_fused / spatial_dropout_fused (same seed) of the materialised
+// gather. fp32 only gathers (p must be 0). The table's rows must be dense
+// (a row-slice view is fine). The values of `starts` are the caller's to
+// validate: 0 <= starts[b] <= N - window.
+torch::Tensor window_batch(torch::Tensor table, torch::Tensor starts,
+                           int64_t window, double p, int64_t seed,
+                           bool spatial) {
+    TORCH_CHECK(table.is_cuda() && table.dim() == 2,
+                "window_batch: table must be an (N, F) GPU tensor");
+    const bool bf16 = table.scalar_type() == torch::kBFloat16;
+    TORCH_CHECK(bf16 || table.scalar_type() == torch::kFloat32,
+                "window_batch: table must be bf16 or fp32");
+    const int64_t N = table.size(0), F = table.size(1);
+    TORCH_CHECK(F >= 1 && table.stride(1) == 1 &&
+                (N == 1 || table.stride(0) == F),
+                "window_batch: table rows must be contiguous");
+    TORCH_CHECK(starts.is_cuda() && starts.device() == table.device() &&
+                starts.scalar_type() == torch::kInt64 && starts.dim() == 1 &&
+                starts.is_contiguous(),
+                "window_batch: starts must be a contiguous (B) int64 tensor "
+                "on the table's device");
+    const int64_t B = starts.size(0);
+    TORCH_CHECK(B >= 1, "window_batch: no windows");
+    TORCH_CHECK(window >= 1 && N >= window,
+                "window_batch: window must be in [1, N]");
+    TORCH_CHECK(window <= INT_MAX / F, "window_batch: window * F too large");
+    TORCH_CHECK(p >= 0.0 && p < 1.0, "window_batch: p must be in [0, 1)");
+    TORCH_CHECK(bf16 || p == 0.0,
+                "window_batch: dropout is bf16-only; fp32 takes p == 0");
+    auto out = torch::empty({B, window, F}, table.options());
+    auto stream = at::hip::getCurrentHIPStream();
+    const DropParams dp = drop_params(p);
+    const int mode = p > 0.0 ? (spatial ? 2 : 1) : 0;
+    int rc = fmda_window_batch_launch(
+        bf16 ? 1 : 0, table.data_ptr(),
+        (const long*)starts.data_ptr<int64_t>(), out.data_ptr(), (long)B,
+        (long)window, (long)F, mode, dp.thr, dp.scale,
+        (unsigned long long)seed, stream.stream());
+    TORCH_CHECK(rc == 0, "window_batch launch failed rc=", rc);
+    return out;
+}
+
 void ingest_row(torch::Tensor ring, torch::Tensor row, torch::Tensor xmin,
                 torch::Tensor xrng) {
     TORCH_CHECK(ring.is_cuda() && ring.is_contiguous() && ring.dim() == 2 &&
@@ -949,6 +998,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("normalize_table", &normalize_table,
           "nan_to_num + min/max normalisation of a raw (N, F) table",
           py::arg("x"), py::arg("x_min"), py::arg("x_max"), py::arg("dtype"));
+    m.def("window_batch", &window_batch,
+          "gather windows of a table into a (B, T, F) batch with fused "
+          "(spatial) input dropout",
+          py::arg("table"), py::arg("starts"), py::arg("window"),
+          py::arg("p"), py::arg("seed"), py::arg("spatial"));
     m.def("gru_bwd", &gru_bwd, "fused biGRU recurrence backward (HIP/CDNA4)",
           py::arg("gi"), py::arg("w"), py::arg("bhh"), py::arg("out"),
           py::arg("dout"), py::arg("dhT"), py::arg("drop_p") = 0.0,

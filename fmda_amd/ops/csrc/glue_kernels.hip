@@ -15,6 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <cstdint>
+
+#include "dropout_common.h"   // mix64, drop_hit, drop_apply
+
 #define FMDA_DEV __device__ __forceinline__
 
 namespace fmda {
@@ -337,6 +341,136 @@ __global__ void normalize_table_kernel(const float* __restrict__ x,
     }
 }
 
+// ===========================================================================
+// window_batch
+// ===========================================================================
+// out (B, T, F) = the windows table[starts[b] : starts[b] + T] of a
+// normalised (N, F) table, with the model's input dropout applied on the
+// way: one write pass, the table stays cache resident. A window is one
+// contiguous slab of the table, so out.flat[b*TF + r] = table.flat[
+// starts[b]*F + r]. The masks are those of dropout_kernel (MODE 1: one draw
+// per flat output octet) and spatial_dropout_kernel (MODE 2: channel id
+// b*F + f) in gru_kernels.hip, through the same dropout_common.h helpers,
+// so the result equals theirs on the materialised batch bit for bit.
+//
+// A thread owns 16 output bytes (V = 8 bf16 / 4 fp32 elements; for bf16
+// that is the dropout octet). The output is 16-byte aligned; the source is
+// not: a window starts at any row and rows are F*sizeof(T) bytes. LB is the
+// width in bytes of the source loads, picked by the launcher from the real
+// alignment of the base pointer and the row pitch. LB > 0 needs TF % V == 0:
+// then no vector straddles two windows and there is no tail. LB == 0 is the
+// element-wise path for everything else: a vector may straddle windows
+// (two unrelated source addresses) and the last one may be partial.
+struct alignas(16) chunk16 { unsigned int u[4]; };
+
+template <int LB>
+FMDA_DEV void load16(void* dst, const void* src) {
+    if constexpr (LB == 16) {
+        *(chunk16*)dst = *(const chunk16*)src;
+    } else if constexpr (LB == 8) {
+        ((uint2*)dst)[0] = ((const uint2*)src)[0];
+        ((uint2*)dst)[1] = ((const uint2*)src)[1];
+    } else {
+        static_assert(LB == 4, "load16: LB is 16, 8 or 4");
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            ((unsigned int*)dst)[k] = ((const unsigned int*)src)[k];
+    }
+}
+
+template <typename T, int LB, int MODE>
+__global__ void window_batch_kernel(const T* __restrict__ table,
+                                    const long* __restrict__ starts,
+                                    T* __restrict__ out, long n, long TF,
+                                    int F, unsigned int thr, float scale,
+                                    unsigned long long seed) {
+    constexpr int V = 16 / (int)sizeof(T);
+    static_assert(MODE == 0 || V == 8, "dropout octets are 8 bf16 elements");
+    const long o = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (o >= n) return;
+    const long b = o / TF;
+    const long r = o - b * TF;
+    const int cnt = (o + V <= n) ? V : (int)(n - o);
+    alignas(16) T v[V];
+    if constexpr (LB > 0) {
+        // r + V <= TF: the 16 bytes lie inside window b, hence in the table
+        load16<LB>(v, table + starts[b] * F + r);
+    } else {
+        long bb = b, rr = r;
+        const T* src = table + starts[bb] * F;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            if (k >= cnt) break;
+            v[k] = src[rr];
+            if (++rr == TF && k + 1 < cnt) {   // o + k + 1 < n: bb + 1 < B
+                rr = 0;
+                src = table + starts[++bb] * F;
+            }
+        }
+    }
+    if constexpr (MODE == 1) {
+        const unsigned long long draw =
+            mix64(seed ^ (unsigned long long)(o >> 3));
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            if (k >= cnt) break;
+            v[k] = from_f32<T>(drop_apply(to_f32<T>(v[k]),
+                                          drop_hit(draw, k, thr), scale));
+        }
+    } else if constexpr (MODE == 2) {
+        long bb = b, rr = r;
+        int f = (int)(r % F);
+        unsigned long long q_last = ~0ull, draw = 0;   // c >> 3 is never ~0
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            if (k >= cnt) break;
+            const long c = bb * F + f;                 // channel id (b, f)
+            const unsigned long long q = (unsigned long long)(c >> 3);
+            if (q != q_last) {
+                draw = mix64(seed ^ q);
+                q_last = q;
+            }
+            v[k] = from_f32<T>(drop_apply(
+                to_f32<T>(v[k]), drop_hit(draw, (int)c & 7, thr), scale));
+            if (++f == F) f = 0;
+            if (++rr == TF) {
+                rr = 0;
+                ++bb;
+            }
+        }
+    }
+    if (cnt == V) {
+        *(chunk16*)(out + o) = *(const chunk16*)v;
+    } else {
+        for (int k = 0; k < cnt; ++k) out[o + k] = v[k];
+    }
+}
+
+template <typename T, int MODE>
+void window_batch_dispatch(int lb, dim3 grid, hipStream_t stream,
+                           const void* table, const long* starts, void* out,
+                           long n, long TF, int F, unsigned int thr,
+                           float scale, unsigned long long seed) {
+#define FMDA_WB(LB)                                                        \
+    window_batch_kernel<T, LB, MODE><<<grid, 256, 0, stream>>>(            \
+        (const T*)table, starts, (T*)out, n, TF, F, thr, scale, seed)
+    if (lb == 16) {
+        FMDA_WB(16);
+    } else if (lb == 8) {
+        FMDA_WB(8);
+    } else {
+        // 4-byte loads are a vector path only for 2-byte elements
+        if constexpr (sizeof(T) < 4) {
+            if (lb == 4) {
+                FMDA_WB(4);
+                return;
+            }
+        }
+        FMDA_WB(0);
+    }
+#undef FMDA_WB
+}
+
 inline int launch_ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 }  // namespace
@@ -441,6 +575,53 @@ extern "C" int fmda_normalize_table_launch(
     else
         normalize_table_kernel<float><<<grid, 256, 0, stream>>>(
             x, xmin, xmax, (float*)y, total, F);
+    return launch_ok();
+}
+
+// Width in bytes of the source loads window_batch may use: the largest
+// power of two <= 16 that divides both the table's base address (storage
+// offset included) and its row pitch F*es, since a window starts at any
+// row. 0 = element-wise: the alignment allows nothing wider than one
+// element, or T*F is no multiple of the 16-byte vector.
+extern "C" int fmda_window_batch_load_bytes(const void* table, long TF,
+                                            long F, int es) {
+    if (TF % (16 / es) != 0) return 0;
+    const uintptr_t addr = (uintptr_t)table;
+    const uintptr_t pitch = (uintptr_t)(F * es);
+    int a = 16;
+    while (a > es && (addr % a != 0 || pitch % a != 0)) a >>= 1;
+    return a > es ? a : 0;
+}
+
+// mode: 0 gather only, 1 dropout_kernel's mask, 2 spatial_dropout_kernel's
+// (bf16 only, like those kernels). (thr, scale) from drop_params().
+extern "C" int fmda_window_batch_launch(
+        int is_bf16, const void* table, const long* starts, void* out,
+        long B, long Tlen, long F, int mode, unsigned int thr, float scale,
+        unsigned long long seed, hipStream_t stream) {
+    if (mode < 0 || mode > 2 || (mode != 0 && !is_bf16)) return -2;
+    const int es = is_bf16 ? 2 : 4;
+    const long TF = Tlen * F;
+    const long n = B * TF;
+    if (n == 0) return 0;
+    const int lb = fmda_window_batch_load_bytes(table, TF, F, es);
+    const long threads = (n + 16 / es - 1) / (16 / es);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (!is_bf16)
+        window_batch_dispatch<float, 0>(lb, grid, stream, table, starts, out,
+                                        n, TF, (int)F, thr, scale, seed);
+    else if (mode == 0)
+        window_batch_dispatch<__hip_bfloat16, 0>(
+            lb, grid, stream, table, starts, out, n, TF, (int)F, thr, scale,
+            seed);
+    else if (mode == 1)
+        window_batch_dispatch<__hip_bfloat16, 1>(
+            lb, grid, stream, table, starts, out, n, TF, (int)F, thr, scale,
+            seed);
+    else
+        window_batch_dispatch<__hip_bfloat16, 2>(
+            lb, grid, stream, table, starts, out, n, TF, (int)F, thr, scale,
+            seed);
     return launch_ok();
 }
 

@@ -43,6 +43,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "dropout_common.h"   // mix64, drop_hit, drop_apply
+
 #define FMDA_DEV __device__ __forceinline__
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -234,13 +236,6 @@ struct TilePrefetch {
 // The fp32 path computes the same owned C elements with plain dots so the
 // fused gate phase is identical for both dtypes.
 // ---------------------------------------------------------------------------
-
-FMDA_DEV unsigned long long mix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 // B-fragment of W for the gh GEMM (N = gate output column, K = h index).
 template <int Hp>
@@ -2563,19 +2558,14 @@ __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y,
         T v[8];
         *(chunk16*)v = *(const chunk16*)(x + o);  // bf16 x8 = 16 B
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const unsigned int u = (unsigned int)(r >> (8 * k)) & 0xFF;
-            v[k] = (u < thr) ? from_f32<T>(0.0f)
-                             : from_f32<T>(to_f32<T>(v[k]) * scale);
-        }
+        for (int k = 0; k < 8; ++k)
+            v[k] = from_f32<T>(drop_apply(to_f32<T>(v[k]),
+                                          drop_hit(r, k, thr), scale));
         *(chunk16*)(y + o) = *(const chunk16*)v;
     } else {
-        for (long i = o; i < n; ++i) {
-            const unsigned int u =
-                (unsigned int)(r >> (8 * (i - o))) & 0xFF;
-            y[i] = (u < thr) ? from_f32<T>(0.0f)
-                             : from_f32<T>(to_f32<T>(x[i]) * scale);
-        }
+        for (long i = o; i < n; ++i)
+            y[i] = from_f32<T>(drop_apply(
+                to_f32<T>(x[i]), drop_hit(r, (int)(i - o), thr), scale));
     }
 }
 
@@ -2623,9 +2613,8 @@ __global__ void spatial_dropout_kernel(const T* __restrict__ x,
         const long c = (i / TF) * F + (i % F);   // channel id (b, f)
         const unsigned long long r =
             mix64(seed ^ (unsigned long long)(c >> 3));
-        const unsigned int u = (unsigned int)(r >> (8 * ((int)c & 7))) & 0xFF;
-        v[k] = (u < thr) ? from_f32<T>(0.0f)
-                         : from_f32<T>(to_f32<T>(v[k]) * scale);
+        v[k] = from_f32<T>(drop_apply(to_f32<T>(v[k]),
+                                      drop_hit(r, (int)c & 7, thr), scale));
     }
     if (cnt == 8)
         *(chunk16*)(y + o) = *(const chunk16*)v;

@@ -255,6 +255,66 @@ def fused_spatial_dropout(x: torch.Tensor, p: float) -> torch.Tensor:
     return _FusedSpatialDropout.apply(x, p, seed)
 
 
+def window_batch(table: torch.Tensor, starts: torch.Tensor, window: int,
+                 p: float = 0.0, spatial: bool = False,
+                 seed: Optional[int] = None) -> torch.Tensor:
+    """(B, window, F) training batch of the windows
+    table[starts[b] : starts[b] + window] of a normalised (N, F) table,
+    with training-mode input dropout (`spatial`: whole (b, f) channels)
+    applied on the way. The table is data: there is no backward.
+
+    bf16 on the GPU: one HIP kernel writes the dropped batch straight from
+    the table; the result is bit for bit fused_dropout /
+    fused_spatial_dropout of the materialised gather under the same seed.
+    fp32 on the GPU gathers with the kernel and takes torch's dropout
+    afterwards, CPU tables are indexed: the fallbacks of those two
+    functions. seed=None draws one seed from the CPU generator exactly as
+    they do (only when a bf16 kernel mask is needed).
+
+    `starts` on the CPU is validated here (0 <= starts <= N - window,
+    ValueError before any launch) and uploaded; a `starts` that already
+    lives on the table's device is used as is: the caller has validated it,
+    checking it here would cost a device sync per batch.
+    FMDA_NATIVE_GLUE=0 runs an eager gather followed by the existing
+    dropout call (A/B runs on one build)."""
+    assert not table.requires_grad, "window_batch: the table is data"
+    assert table.dim() == 2 and starts.dim() == 1
+    N = table.size(0)
+    if window < 1 or window > N:
+        raise ValueError(f"window {window} outside [1, {N}]")
+    if starts.dtype != torch.int64:
+        raise TypeError("window_batch: starts must be int64")
+    if starts.numel() < 1:
+        raise ValueError("window_batch: no windows")
+    if not starts.is_cuda:
+        lo, hi = int(starts.min()), int(starts.max())
+        if lo < 0 or hi > N - window:
+            raise ValueError(
+                f"window starts [{lo}, {hi}] outside [0, {N - window}]")
+        starts = starts.to(table.device)
+    kernel_drop = (table.is_cuda and table.dtype == torch.bfloat16
+                   and 0.0 < p < 1.0)
+    if (table.is_cuda and _native_glue()
+            and table.dtype in (torch.bfloat16, torch.float32)):
+        if kernel_drop:
+            if seed is None:
+                seed = int(torch.empty((), dtype=torch.int64).random_())
+            return load_extension().window_batch(table, starts, window, p,
+                                                 seed, spatial)
+        x = load_extension().window_batch(table, starts, window, 0.0, 0,
+                                          False)
+    else:
+        idx = starts[:, None] + torch.arange(window, device=starts.device)
+        x = table[idx]
+        if kernel_drop and seed is not None:
+            ext = load_extension()
+            return (ext.spatial_dropout_fused(x, p, seed) if spatial
+                    else ext.dropout_fused(x, p, seed))
+    if not p > 0.0:
+        return x
+    return fused_spatial_dropout(x, p) if spatial else fused_dropout(x, p)
+
+
 class _DirSumPool(torch.autograd.Function):
     """Fused direction-sum + max/avg temporal pooling on the HIP engine
     (biGRU_model.py:108-133 semantics). Returns (max (B,H), avg (B,H)) in

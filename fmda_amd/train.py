@@ -87,6 +87,45 @@ def evaluate_chunks_windowed(model, market, chunk_set, dcfg, batch_size):
             pred_total, target_total)
 
 
+_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def train_chunks_windowed(model, market, chunk_set, dcfg, tcfg):
+    """model.train_model(chunk_batches(...)) with each chunk kept on the
+    device as one normalised table (BiGRU.train_windows): no DataLoader,
+    no per-step host gather or host-to-device copy. chunk_batches' batching
+    (groups of `batch_size` consecutive windows that never span two chunks,
+    the last partial one kept); returns train_model's 4-tuple, the
+    per-batch values averaged over all chunks. On the GPU the raw chunk is
+    uploaded once and normalised there in `tcfg.dtype`; on CPU the table is
+    BatchLoader's own (fp32), which makes the CPU path the oracle."""
+    import numpy as np
+    X = market.X[:, :dcfg.n_features]
+    accs, hams, losses, fbetas = [], [], [], []
+    for indices, norms in chunk_set:
+        if model.device.type == "cuda":
+            from .ops import load_extension
+            ids = torch.tensor(list(indices), dtype=torch.long) - 1
+            dev = model.device
+            table = load_extension().normalize_table(
+                X[ids].float().contiguous().to(dev),
+                norms[0][0].float().contiguous().to(dev),
+                norms[1][0].float().contiguous().to(dev),
+                _DTYPES[tcfg.dtype])
+            targets = torch.nan_to_num(market.Y[ids], nan=0.0)
+        else:
+            bl = BatchLoader(indices, norms, X, market.Y, dcfg.window)
+            table, targets = bl.x, bl.y
+        a, h, l, f = model.train_windows(table, targets, dcfg.window,
+                                         tcfg.batch_size)
+        accs += a
+        hams += h
+        losses += l
+        fbetas += f
+    return (np.mean(accs), np.mean(hams), np.mean(losses),
+            np.mean(fbetas, axis=0))
+
+
 def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
           tcfg: TrainConfig = None, checkpoint_path: str = "model_params.pt",
           norm_params_path: str = "norm_params", log=print,
@@ -114,7 +153,13 @@ def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
                   bidirectional=mcfg.bidirectional).to(device)
     model.add_loss_fn(nn.BCEWithLogitsLoss(weight=weight.to(device),
                                            pos_weight=pos_weight.to(device)))
-    model.add_optimizer(torch.optim.Adam(model.parameters(), lr=tcfg.lr))
+    if tcfg.windowed_train and device.type == "cuda":
+        # the benched step: fused global-norm clip + Adam in two launches
+        from .optim import FusedClipAdam
+        model.add_optimizer(FusedClipAdam(model.parameters(), lr=tcfg.lr,
+                                          clip=mcfg.clip))
+    else:
+        model.add_optimizer(torch.optim.Adam(model.parameters(), lr=tcfg.lr))
     model.add_device(device)
     if resume:
         # mid-training resume (reference only ever saves, predict.py:104
@@ -143,7 +188,8 @@ def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
             model.load_state_dict(ts["model"], strict=False)
             model.optimizer.load_state_dict(ts["optimizer"])
             start_epoch = ts["epoch"] + 1
-            torch.set_rng_state(ts["rng"])
+            # the CPU generator's state (map_location moved it with the rest)
+            torch.set_rng_state(ts["rng"].cpu())
 
     def evaluate(chunk_set):
         if tcfg.windowed_eval:
@@ -158,8 +204,11 @@ def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
         t0 = time.time()
         train_set, val_set, _ = make_epoch_sets(market, dcfg,
                                                 norm_params_path)
-        tr = model.train_model(
-            chunk_batches(market, train_set, dcfg, tcfg.batch_size))
+        if tcfg.windowed_train:
+            tr = train_chunks_windowed(model, market, train_set, dcfg, tcfg)
+        else:
+            tr = model.train_model(
+                chunk_batches(market, train_set, dcfg, tcfg.batch_size))
         va = evaluate(val_set)
         from .metrics import three_class_accuracy
         rec = {"epoch": epoch, "train_acc": float(tr[0]),
@@ -214,7 +263,7 @@ def train(mcfg: ModelConfig = None, dcfg: DataConfig = None,
     return model, history
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=25)
     ap.add_argument("--hidden", type=int, default=32)
@@ -226,6 +275,13 @@ def main():
     ap.add_argument("--windowed-eval", action="store_true",
                     help="validate / test each chunk as one table through "
                          "BiGRU.evaluate_windows (no materialised windows)")
+    ap.add_argument("--windowed-train", action="store_true",
+                    help="train each chunk as one table kept on the device "
+                         "(BiGRU.train_windows: fused window gather + "
+                         "dropout, fused head+loss, FusedClipAdam on the "
+                         "GPU; no DataLoader in the training loop)")
+    ap.add_argument("--dtype", choices=sorted(_DTYPES), default="fp32",
+                    help="GPU compute dtype of the --windowed-train tables")
     ap.add_argument("--checkpoint", default="model_params.pt")
     ap.add_argument("--resume", default=None,
                     help="checkpoint to resume from (model_params.pt format)")
@@ -234,13 +290,24 @@ def main():
     ap.add_argument("--plots", default=None,
                     help="directory for learning-curve / confusion plots "
                          "(the notebook's cells 30-31 figures)")
-    args = ap.parse_args()
+    return ap
+
+
+def configs_from_args(args):
+    """(ModelConfig, DataConfig, TrainConfig) of parsed CLI arguments."""
     mcfg = ModelConfig(hidden_size=args.hidden, n_layers=args.layers,
                        spatial_dropout=False, dropout=0.5)
     dcfg = DataConfig(n_rows=args.rows, window=args.window)
     tcfg = TrainConfig(batch_size=args.batch, epochs=args.epochs,
-                       device=args.device,
-                       windowed_eval=args.windowed_eval)
+                       device=args.device, dtype=args.dtype,
+                       windowed_eval=args.windowed_eval,
+                       windowed_train=args.windowed_train)
+    return mcfg, dcfg, tcfg
+
+
+def main():
+    args = build_parser().parse_args()
+    mcfg, dcfg, tcfg = configs_from_args(args)
     if args.log_file:
         fh = open(args.log_file, "a")
 
