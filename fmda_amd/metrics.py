@@ -12,7 +12,24 @@ import torch
 
 
 def subset_accuracy(target: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
-    """sklearn.metrics.accuracy_score on multilabel data: exact-match ratio."""
+    """sklearn.metrics.accuracy_score on multilabel data: exact-match ratio.
+
+    On the GPU, a contiguous 2-D float32 / bool target with a contiguous
+    bool pred of up to 65536 rows is counted by one HIP kernel (the training
+    loop calls this every step); it returns the value of the expression
+    below, scaled as torch's mean scales (count * float(1/N)). Everything
+    else, and FMDA_NATIVE_GLUE=0, evaluates the expression itself."""
+    if (target.is_cuda and pred.is_cuda and pred.dtype == torch.bool
+            and target.dtype in (torch.float32, torch.bool)
+            and target.dim() == 2 and target.shape == pred.shape
+            and target.device == pred.device
+            and 1 <= target.shape[0] <= 65536
+            and 1 <= target.shape[1] <= 65536
+            and target.is_contiguous() and pred.is_contiguous()):
+        from .ops import load_extension
+        from .ops.interface import _native_glue
+        if _native_glue():
+            return load_extension().subset_accuracy(target, pred)
     t = target.to(torch.bool)
     p = pred.to(torch.bool)
     return (t == p).all(dim=1).float().mean()

@@ -71,17 +71,24 @@ def chunked_outer(dg: torch.Tensor, x: torch.Tensor,
     return s if out_fp32 else s.to(dg.dtype)
 
 
-def chunked_outer_parts(dg: torch.Tensor, x: torch.Tensor,
-                        chunks: int = 64) -> torch.Tensor:
-    """The raw split-K partials of `chunked_outer`: (c, N, K) in the input
-    dtype, whose sum over c is (M, N)^T @ (M, K). c is the largest halving
-    of `chunks` that divides M; with no even split it is 1 (one plain
-    GEMM). For callers that reduce the partials themselves."""
-    M, N = dg.shape
-    K = x.shape[1]
+def split_chunks(M: int, chunks: int = 64) -> int:
+    """Number of split-K chunks `chunked_outer_parts` cuts M rows into: the
+    largest halving of `chunks` that divides M, 1 with no even split."""
     c = chunks
     while c > 1 and M % c != 0:
         c //= 2
+    return max(c, 1)
+
+
+def chunked_outer_parts(dg: torch.Tensor, x: torch.Tensor,
+                        chunks: int = 64) -> torch.Tensor:
+    """The raw split-K partials of `chunked_outer`: (c, N, K) in the input
+    dtype, whose sum over c is (M, N)^T @ (M, K). c is split_chunks(M); with
+    no even split it is 1 (one plain GEMM). For callers that reduce the
+    partials themselves."""
+    M, N = dg.shape
+    K = x.shape[1]
+    c = split_chunks(M, chunks)
     if c <= 1:
         return torch.matmul(dg.t(), x).unsqueeze(0)
     return torch.bmm(dg.view(c, M // c, N).transpose(1, 2),

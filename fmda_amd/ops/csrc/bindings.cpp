@@ -111,15 +111,27 @@ extern "C" int fmda_finalize_gru_wgrads_launch(
         int part_bf16, const void* part_ih, int c_ih, const void* part_hh,
         int c_hh, float* const* grads, int D, int H, int Hp, int F,
         hipStream_t stream);
+extern "C" int fmda_finalize_gru_wgrads_eager_launch(
+        int part_bf16, const void* part_ih, const void* part_hh,
+        float* const* grads, int D, int H, int Hp, int F,
+        hipStream_t stream);
+extern "C" int fmda_eager_sum_chunks();
+extern "C" int fmda_head_wgrads_eager_launch(
+        int is_bf16, const void* parts, const float* db_sum, float* dW,
+        float* db, int K, int C, hipStream_t stream);
+extern "C" int fmda_subset_accuracy_launch(
+        int target_is_float, const void* target, const void* pred,
+        float* out, int B, int C, hipStream_t stream);
 extern "C" int fmda_head_fwd_master_launch(
         int is_bf16, const void* x, const float* W, const float* bias,
         const float* y, const float* wgt, const float* pw, float* logits,
-        float* sig, float* loss_sum, int B, int K, int C,
+        float* sig, float* loss_sum, int B, int K, int C, int staged,
         hipStream_t stream);
 extern "C" int fmda_head_bwd_master_launch(
         int is_bf16, const float* sig, const float* y, const float* wgt,
         const float* pw, const float* gscale, const float* W,
-        float* dlogits, void* dx, int B, int K, int C, hipStream_t stream);
+        float* dlogits, void* dlogits_t, void* dx, int B, int K, int C,
+        hipStream_t stream);
 extern "C" int fmda_normalize_table_launch(
         int out_bf16, const float* x, const float* xmin, const float* xmax,
         void* y, long N, int F, hipStream_t stream);
@@ -867,13 +879,28 @@ std::vector<torch::Tensor> pack_gru_layer(std::vector<torch::Tensor> masters,
     return {w_ih_cat, b_ih_cat, w_hh_cat, b_hh_cat, wt};
 }
 
+// Whether the native kernels know the order in which torch sums these
+// (c, N, K) split-K partials over c. It is derived for ATen's 64 x 2 reduce
+// block: 64 chunks, at least 512 outputs, whole vectors of 4.
+bool eager_sum_applies(torch::Tensor parts) {
+    if (parts.dim() != 3 || parts.size(0) != fmda_eager_sum_chunks())
+        return false;
+    const int64_t outputs = parts.size(1) * parts.size(2);
+    return outputs >= 512 && outputs % 4 == 0;
+}
+
 // part_ih: (c, D*3Hp, F) split-K partials of dGi^T x; part_hh:
 // (c, D*3Hp, D*Hp) partials of dGh^T out. Returns the fp32 master-shaped
 // {dW_ih[0] (3H,F), dW_hh[0] (3H,H), dW_ih[1], dW_hh[1]}.
+// eager_order: sum the chunks in the order of parts.float().sum(dim=0), so
+// the grads equal the eager chain's bit for bit; only for partials
+// eager_sum_applies() accepts.
+
 std::vector<torch::Tensor> finalize_gru_wgrads(torch::Tensor part_ih,
                                                torch::Tensor part_hh,
                                                int64_t D, int64_t H,
-                                               int64_t Hp) {
+                                               int64_t Hp,
+                                               bool eager_order) {
     TORCH_CHECK(part_ih.is_cuda() && part_hh.is_cuda() &&
                 part_ih.is_contiguous() && part_hh.is_contiguous() &&
                 part_ih.dim() == 3 && part_hh.dim() == 3,
@@ -898,10 +925,20 @@ std::vector<torch::Tensor> finalize_gru_wgrads(torch::Tensor part_ih,
         ptrs[2 * d + 1] = grads[2 * d + 1].data_ptr<float>();
     }
     auto stream = at::hip::getCurrentHIPStream();
-    int rc = fmda_finalize_gru_wgrads_launch(
-        bf16 ? 1 : 0, part_ih.data_ptr(), (int)part_ih.size(0),
-        part_hh.data_ptr(), (int)part_hh.size(0), ptrs, (int)D, (int)H,
-        (int)Hp, (int)F, stream.stream());
+    int rc;
+    if (eager_order) {
+        TORCH_CHECK(eager_sum_applies(part_ih) && eager_sum_applies(part_hh),
+                    "finalize_gru_wgrads: the eager sum order is known only "
+                    "for 64 chunks of >= 512 outputs, a multiple of 4");
+        rc = fmda_finalize_gru_wgrads_eager_launch(
+            bf16 ? 1 : 0, part_ih.data_ptr(), part_hh.data_ptr(), ptrs,
+            (int)D, (int)H, (int)Hp, (int)F, stream.stream());
+    } else {
+        rc = fmda_finalize_gru_wgrads_launch(
+            bf16 ? 1 : 0, part_ih.data_ptr(), (int)part_ih.size(0),
+            part_hh.data_ptr(), (int)part_hh.size(0), ptrs, (int)D, (int)H,
+            (int)Hp, (int)F, stream.stream());
+    }
     TORCH_CHECK(rc == 0, "finalize_gru_wgrads launch failed");
     return grads;
 }
@@ -911,7 +948,9 @@ std::vector<torch::Tensor> finalize_gru_wgrads(torch::Tensor part_ih,
 // b.to(x) bit for bit.
 std::vector<torch::Tensor> head_loss_fwd_master(
         torch::Tensor x, torch::Tensor W, torch::Tensor b, torch::Tensor y,
-        torch::Tensor wgt, torch::Tensor pw) {
+        torch::Tensor wgt, torch::Tensor pw, bool staged) {
+    // staged: read x and W through LDS (same bits); false keeps the direct
+    // kernel reachable as the reference
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2);
     const bool bf16 = compute_dtype_is_bf16(x.scalar_type());
     check_f32_cuda(W, "head W"); check_f32_cuda(b, "head b");
@@ -930,15 +969,17 @@ std::vector<torch::Tensor> head_loss_fwd_master(
         bf16 ? 1 : 0, x.data_ptr(), W.data_ptr<float>(), b.data_ptr<float>(),
         y.data_ptr<float>(), wgt.data_ptr<float>(), pw.data_ptr<float>(),
         logits.data_ptr<float>(), sig.data_ptr<float>(),
-        part.data_ptr<float>(), B, K, C, stream.stream());
+        part.data_ptr<float>(), B, K, C, staged ? 1 : 0, stream.stream());
     TORCH_CHECK(rc == 0, "head fwd (master) launch failed");
-    return {logits, sig, part.sum().reshape({1})};
+    return {logits, sig, part.sum().reshape({1}), part};
 }
 
 std::vector<torch::Tensor> head_loss_bwd_master(
         torch::Tensor sig, torch::Tensor y, torch::Tensor wgt,
         torch::Tensor pw, torch::Tensor gscale, torch::Tensor W,
-        torch::ScalarType xdtype) {
+        torch::ScalarType xdtype, bool emit_cast) {
+    // emit_cast: also return dlogits.to(xdtype), written by the same kernel
+    // (dlogits itself when xdtype is fp32)
     check_f32_cuda(sig, "head sig"); check_f32_cuda(y, "head y");
     check_f32_cuda(wgt, "head weight"); check_f32_cuda(pw, "head pos_weight");
     check_f32_cuda(gscale, "head gscale"); check_f32_cuda(W, "head W");
@@ -949,14 +990,71 @@ std::vector<torch::Tensor> head_loss_bwd_master(
     const bool bf16 = compute_dtype_is_bf16(xdtype);
     auto dlogits = torch::empty_like(sig);
     auto dx = torch::empty({B, K}, sig.options().dtype(xdtype));
+    torch::Tensor dl_t;
+    if (emit_cast && bf16)
+        dl_t = torch::empty({B, C}, sig.options().dtype(xdtype));
     auto stream = at::hip::getCurrentHIPStream();
     int rc = fmda_head_bwd_master_launch(
         bf16 ? 1 : 0, sig.data_ptr<float>(), y.data_ptr<float>(),
         wgt.data_ptr<float>(), pw.data_ptr<float>(),
         gscale.data_ptr<float>(), W.data_ptr<float>(),
-        dlogits.data_ptr<float>(), dx.data_ptr(), B, K, C, stream.stream());
+        dlogits.data_ptr<float>(), dl_t.defined() ? dl_t.data_ptr() : nullptr,
+        dx.data_ptr(), B, K, C, stream.stream());
     TORCH_CHECK(rc == 0, "head bwd (master) launch failed");
-    return {dlogits, dx};
+    if (!emit_cast) return {dlogits, dx};
+    return {dlogits, dx, bf16 ? dl_t : dlogits};
+}
+
+// dW (C, K) and db (C) of the head as the eager chain leaves them: parts
+// (64, C, K) are the split-K partials of dlogits.to(x)^T x, db_sum is
+// dlogits.sum(0). dW = parts.float().sum(0).to(x).to(fp32) in that sum's
+// order, db = db_sum.to(x).to(fp32); one launch.
+std::vector<torch::Tensor> head_wgrads_eager(torch::Tensor parts,
+                                             torch::Tensor db_sum) {
+    TORCH_CHECK(parts.is_cuda() && parts.is_contiguous() &&
+                eager_sum_applies(parts),
+                "head_wgrads_eager: parts must be contiguous (64, C, K) GPU "
+                "partials with C*K >= 512, a multiple of 4");
+    check_f32_cuda(db_sum, "head db_sum");
+    const bool bf16 = compute_dtype_is_bf16(parts.scalar_type());
+    const int C = parts.size(1), K = parts.size(2);
+    TORCH_CHECK(db_sum.numel() == C && db_sum.is_contiguous(),
+                "head_wgrads_eager: shape mismatch");
+    auto f32 = db_sum.options();
+    auto dW = torch::empty({C, K}, f32);
+    auto db = torch::empty({C}, f32);
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_head_wgrads_eager_launch(
+        bf16 ? 1 : 0, parts.data_ptr(), db_sum.data_ptr<float>(),
+        dW.data_ptr<float>(), db.data_ptr<float>(), K, C, stream.stream());
+    TORCH_CHECK(rc == 0, "head_wgrads_eager launch failed");
+    return {dW, db};
+}
+
+// Exact-match ratio of a (B, C) batch: target fp32 or bool, pred bool, both
+// contiguous. 0-dim fp32, the value of
+// (target.bool() == pred).all(1).float().mean().
+torch::Tensor subset_accuracy(torch::Tensor target, torch::Tensor pred) {
+    TORCH_CHECK(target.is_cuda() && pred.is_cuda() && target.dim() == 2 &&
+                target.sizes() == pred.sizes() && target.is_contiguous() &&
+                pred.is_contiguous() && pred.scalar_type() == torch::kBool &&
+                target.device() == pred.device(),
+                "subset_accuracy: need contiguous (B, C) GPU tensors, pred "
+                "bool");
+    const bool tf = target.scalar_type() == torch::kFloat32;
+    TORCH_CHECK(tf || target.scalar_type() == torch::kBool,
+                "subset_accuracy: target must be fp32 or bool");
+    const int64_t B = target.size(0), C = target.size(1);
+    // one block walks the rows; the count stays exact in fp32
+    TORCH_CHECK(B >= 1 && B <= (1 << 16) && C >= 1 && C <= (1 << 16),
+                "subset_accuracy: 1 <= B, C <= 65536");
+    auto out = torch::empty({}, target.options().dtype(torch::kFloat32));
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_subset_accuracy_launch(
+        tf ? 1 : 0, target.data_ptr(), pred.data_ptr(),
+        out.data_ptr<float>(), (int)B, (int)C, stream.stream());
+    TORCH_CHECK(rc == 0, "subset_accuracy launch failed");
+    return out;
 }
 
 // dW (C, K) = round_x(dlogits)^T x and db (C) = sum_rows dlogits, both fp32,
@@ -1034,11 +1132,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pack_gru_layer", &pack_gru_layer,
           "fp32 masters -> padded compute-dtype layer weights (+ W_hh^T)");
     m.def("finalize_gru_wgrads", &finalize_gru_wgrads,
-          "split-K partials -> master-shaped fp32 dW_ih / dW_hh");
+          "split-K partials -> master-shaped fp32 dW_ih / dW_hh",
+          py::arg("part_ih"), py::arg("part_hh"), py::arg("D"), py::arg("H"),
+          py::arg("Hp"), py::arg("eager_order") = false);
+    m.def("eager_sum_applies", &eager_sum_applies,
+          "whether the eager chunk-sum order is known for these partials");
     m.def("head_loss_fwd_master", &head_loss_fwd_master,
-          "fused head GEMM + BCE loss reading the fp32 master W / b");
+          "fused head GEMM + BCE loss reading the fp32 master W / b; "
+          "returns (logits, sig, loss_sum, block partials)",
+          py::arg("x"), py::arg("W"), py::arg("b"), py::arg("y"),
+          py::arg("wgt"), py::arg("pw"), py::arg("staged") = true);
     m.def("head_loss_bwd_master", &head_loss_bwd_master,
-          "fused head/loss backward reading the fp32 master W");
+          "fused head/loss backward reading the fp32 master W",
+          py::arg("sig"), py::arg("y"), py::arg("wgt"), py::arg("pw"),
+          py::arg("gscale"), py::arg("W"), py::arg("xdtype"),
+          py::arg("emit_cast") = false);
+    m.def("head_wgrads_eager", &head_wgrads_eager,
+          "head dW / db from the split-K partials, the eager chain's bits");
+    m.def("subset_accuracy", &subset_accuracy,
+          "exact-match ratio of a (B, C) multilabel batch in one kernel");
     m.def("head_wgrads", &head_wgrads,
           "head dW / db in fp32, two-stage fixed-order batch reduction");
     m.def("fused_clip_adam", &fused_clip_adam,

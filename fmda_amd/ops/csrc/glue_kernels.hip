@@ -9,6 +9,10 @@
 //                        fp32 weight gradients of a layer
 //   head_*_master        classifier head + loss reading the fp32 masters
 //   head_wgrads          dW / db of the head, two-stage over the batch
+//   *_eager kernels      the two weight-grad reductions over 64 split-K
+//                        chunks in the order of torch's own sum: the eager
+//                        chain's bits in one launch
+//   subset_accuracy      the step's exact-match metric in one launch
 // All sums run in a fixed order: results are bitwise reproducible.
 // Inference side: normalize_table, the raw (N, F) table -> normalised
 // compute-dtype table in one pass (windowed evaluation of whole chunks).
@@ -47,6 +51,8 @@ template <> FMDA_DEV __hip_bfloat16 from_f32<__hip_bfloat16>(float v) {
 template <typename T> FMDA_DEV float round_to(float v) {
     return to_f32<T>(from_f32<T>(v));
 }
+// 16 bytes moved as one vector load / store
+struct alignas(16) chunk16 { unsigned int u[4]; };
 
 // ===========================================================================
 // pack_gru_layer
@@ -165,6 +171,111 @@ __global__ void finalize_gru_wgrads_kernel(const PT* __restrict__ part_ih,
     }
 }
 
+// ---------------------------------------------------------------------------
+// The same reductions in the order of torch's `parts.float().sum(dim=0)`
+// for c = 64 chunks, so the result equals the eager chain bit for bit.
+// ATen's reduce kernel (slow-dimension reduction, contiguous outputs, at
+// least 512 of them and a multiple of 4) runs a 64 x 2 block: row y of the
+// block takes the chunks k = y + 2m, m = 0..31, in four accumulators that
+// start at 0.0f, accumulator i taking m = i (mod 4) in ascending m; the
+// accumulators are combined as ((a0 + a1) + a2) + a3 and the two rows are
+// added once. The launchers' callers check those conditions.
+// ---------------------------------------------------------------------------
+constexpr int EAGER_SUM_CHUNKS = 64;
+
+template <int BYTES> struct raw_vec;
+template <> struct raw_vec<2> { using type = unsigned short; };
+template <> struct raw_vec<4> { using type = unsigned int; };
+template <> struct raw_vec<8> { using type = uint2; };
+template <> struct raw_vec<16> { using type = uint4; };
+
+// out[j] = sum over the 64 chunks of p[k * cs + j], j < V, in that order.
+// p + k * cs is aligned to V elements.
+template <typename PT, int V>
+FMDA_DEV void eager_order_sum64(const PT* __restrict__ p, long cs,
+                                float (&out)[V]) {
+    using raw_t = typename raw_vec<V * (int)sizeof(PT)>::type;
+    float row[2][V];
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+        float a[4][V];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < V; ++j) a[i][j] = 0.0f;
+#pragma unroll
+        for (int n = 0; n < EAGER_SUM_CHUNKS / 8; ++n) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                alignas(V * sizeof(PT)) PT v[V];
+                *(raw_t*)v = *(const raw_t*)(p + (y + 2 * (4 * n + i)) * cs);
+#pragma unroll
+                for (int j = 0; j < V; ++j) a[i][j] += to_f32<PT>(v[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+            row[y][j] = ((a[0][j] + a[1][j]) + a[2][j]) + a[3][j];
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) out[j] = row[0][j] + row[1][j];
+}
+
+// finalize_gru_wgrads_kernel with eager_order_sum64 over c = 64 chunks of
+// both partials. One thread per V consecutive outputs of one row (V divides
+// H and F, so a vector never leaves its row).
+template <typename PT, int V>
+__global__ void __launch_bounds__(256) finalize_gru_wgrads_eager_kernel(
+        const PT* __restrict__ part_ih, const PT* __restrict__ part_hh,
+        GruWgrads o, int D, int H, int Hp, int F) {
+    const long n_ih = 3L * H * F;
+    const long n_hh = 3L * H * H;
+    const long per_dir = n_ih + n_hh;
+    const long idx = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (idx >= (long)D * per_dir) return;
+    const int d = (int)(idx / per_dir);
+    const long r = idx % per_dir;
+    float acc[V];
+    float* dst;
+    if (r < n_ih) {
+        const int row = (int)(r / F), col = (int)(r % F);
+        const long prow = (long)d * 3 * Hp + (long)(row / H) * Hp + row % H;
+        eager_order_sum64<PT, V>(part_ih + prow * F + col,
+                                 (long)D * 3 * Hp * F, acc);
+        dst = o.dw_ih[d] + r;
+    } else {
+        const long q = r - n_ih;
+        const int row = (int)(q / H), col = (int)(q % H);
+        const long prow = (long)d * 3 * Hp + (long)(row / H) * Hp + row % H;
+        const long pitch = (long)D * Hp;
+        eager_order_sum64<PT, V>(part_hh + prow * pitch + (long)d * Hp + col,
+                                 (long)D * 3 * Hp * pitch, acc);
+        dst = o.dw_hh[d] + q;
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) dst[j] = acc[j];
+}
+
+// Head weight grads from the (64, C, K) split-K partials of
+// round_T(dlogits)^T x: dW = fp32(T(sum of the chunks in the eager order)),
+// and db = fp32(T(db_sum)) for the batch sum torch already made. That is
+// chunked_outer(...).to(fp32) and dlogits.sum(0).to(T).to(fp32).
+template <typename T>
+__global__ void head_wgrads_eager_kernel(const T* __restrict__ parts,
+                                         const float* __restrict__ db_sum,
+                                         float* __restrict__ dW,
+                                         float* __restrict__ db, int n_w,
+                                         int C) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n_w) {
+        float s[1];
+        eager_order_sum64<T, 1>(parts + idx, (long)n_w, s);
+        dW[idx] = round_to<T>(s[0]);
+    } else if (idx < n_w + C) {
+        db[idx - n_w] = round_to<T>(db_sum[idx - n_w]);
+    }
+}
+
 // ===========================================================================
 // Classifier head + BCEWithLogitsLoss(weight, pos_weight) on the fp32
 // master W / b. The arithmetic is head_loss_{fwd,bwd}_kernel's
@@ -217,6 +328,102 @@ __global__ void head_fwd_master_kernel(const T* __restrict__ x,
     }
 }
 
+// head_fwd_master_kernel with its operands staged in LDS. The mapping of
+// threads to (row, class), each thread's serial chain over ascending k, the
+// loss expression and the block's butterfly are those of the kernel above,
+// so logits, sig and every block partial are the same bits. What differs is
+// where the chain reads from: above, a wave's lanes walk 64/C rows that lie
+// K*sizeof(T) bytes apart, one element per load. Here the block copies its
+// rows of x (contiguous in memory) into LDS with coalesced 16-byte loads,
+// KT columns at a time, next to the rounded W tile, and the chains run from
+// LDS 16 bytes per read. Row pitches are padded (16 bytes for x, 4 floats
+// for W) to spread the rows over the banks.
+// Dynamic LDS: rows_cap * (KT*sizeof(T) + 16) + C * (KT + 4) * 4 bytes.
+// K and KT are multiples of 16/sizeof(T); x is 16-byte aligned.
+template <typename T>
+__global__ void head_fwd_master_staged_kernel(
+        const T* __restrict__ x, const float* __restrict__ W,
+        const float* __restrict__ bias, const float* __restrict__ y,
+        const float* __restrict__ wgt, const float* __restrict__ pw,
+        float* __restrict__ logits, float* __restrict__ sig,
+        float* __restrict__ loss_sum, int B, int K, int C, int KT,
+        int rows_cap) {
+    constexpr int V = 16 / (int)sizeof(T);
+    extern __shared__ __align__(16) unsigned char head_smem[];
+    const int xpitch = KT * (int)sizeof(T) + 16;   // bytes
+    const int wpitch = KT + 4;                     // floats
+    unsigned char* xs = head_smem;
+    float* ws = (float*)(head_smem + (size_t)rows_cap * xpitch);
+
+    const int first = blockIdx.x * blockDim.x;     // < B * C by the grid
+    const int idx = first + threadIdx.x;
+    const int last = min(first + (int)blockDim.x, B * C) - 1;
+    const int r0 = first / C;
+    const int nrows = last / C - r0 + 1;           // <= rows_cap
+    const bool valid = idx < B * C;
+    const int r = valid ? idx / C : r0, c = valid ? idx % C : 0;
+    float acc = round_to<T>(bias[c]);
+    for (int k0 = 0; k0 < K; k0 += KT) {
+        const int kt = min(KT, K - k0);
+        const int cpr = kt / V;                    // 16-byte chunks per row
+        if (k0 > 0) __syncthreads();               // the last tile is read
+        for (int j = threadIdx.x; j < nrows * cpr; j += blockDim.x) {
+            const int row = j / cpr, cc = j % cpr;
+            *(chunk16*)(xs + row * xpitch + cc * 16) =
+                *(const chunk16*)(x + (long)(r0 + row) * K + k0 + cc * V);
+        }
+        for (int j = threadIdx.x; j < C * kt; j += blockDim.x) {
+            const int cw = j / kt, kk = j % kt;
+            ws[cw * wpitch + kk] = round_to<T>(W[(long)cw * K + k0 + kk]);
+        }
+        __syncthreads();
+        if (valid) {
+            const unsigned char* xr = xs + (r - r0) * xpitch;
+            const float* wr = ws + c * wpitch;
+            for (int kk = 0; kk < kt; kk += V) {
+                alignas(16) T xv[V];
+                alignas(16) float wv[V];
+                *(chunk16*)xv = *(const chunk16*)(xr + kk * (int)sizeof(T));
+#pragma unroll
+                for (int q = 0; q < V / 4; ++q)
+                    *(chunk16*)(wv + 4 * q) =
+                        *(const chunk16*)(wr + kk + 4 * q);
+                // the direct kernel's `acc += x * w` compiles to one fused
+                // multiply-add per k; written out here, because with the
+                // operands in vectors the compiler would otherwise pair the
+                // products into packed multiplies and round them
+#pragma unroll
+                for (int j = 0; j < V; ++j)
+                    acc = __builtin_fmaf(to_f32<T>(xv[j]), wv[j], acc);
+            }
+        }
+    }
+    float l = 0.0f;
+    if (valid) {
+        logits[idx] = acc;
+        const float s = sigmoidf(acc);
+        sig[idx] = s;
+        const float yy = y[idx];
+        const float m = acc > 0.0f ? acc : 0.0f;
+        const float lse = m + __builtin_logf(fast_exp2(-m * FMDA_LOG2E) +
+                                             fast_exp2((acc - m) * FMDA_LOG2E));
+        const float log_s = acc - lse;
+        const float log_1ms = -lse;
+        l = -wgt[c] * (pw[c] * yy * log_s + (1.0f - yy) * log_1ms);
+    }
+    __shared__ float red[4];
+    float v = l;
+    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+        loss_sum[blockIdx.x] = t;
+    }
+}
+
 template <typename T>
 __global__ void head_bwd_master_kernel(const float* __restrict__ sig,
                                        const float* __restrict__ y,
@@ -225,8 +432,11 @@ __global__ void head_bwd_master_kernel(const float* __restrict__ sig,
                                        const float* __restrict__ gscale,
                                        const float* __restrict__ W,
                                        float* __restrict__ dlogits,
+                                       T* __restrict__ dlogits_t,
                                        T* __restrict__ dx, int B, int K,
                                        int C) {
+    // dlogits_t (may be null): dlogits rounded to T, the operand of the
+    // dW GEMM, exactly dlogits.to(T)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * K) return;
     const int r = idx / K, k = idx % K;
@@ -237,7 +447,10 @@ __global__ void head_bwd_master_kernel(const float* __restrict__ sig,
         const float yy = y[r * C + c];
         const float dl = g * wgt[c] * (s * (1.0f - yy + pw[c] * yy) -
                                        pw[c] * yy);
-        if (k == 0) dlogits[r * C + c] = dl;
+        if (k == 0) {
+            dlogits[r * C + c] = dl;
+            if (dlogits_t != nullptr) dlogits_t[r * C + c] = from_f32<T>(dl);
+        }
         acc += dl * round_to<T>(W[(long)c * K + k]);
     }
     dx[idx] = from_f32<T>(acc);
@@ -316,6 +529,44 @@ __global__ void head_wgrads_stage2_kernel(const float* __restrict__ dw_part,
 }
 
 // ===========================================================================
+// subset_accuracy
+// ===========================================================================
+// Exact-match ratio of a (B, C) multilabel batch in one launch and one
+// block: out = count(rows whose labels all match) * inv_b. The count is an
+// integer, so the order it is summed in does not matter; the scaling is
+// torch's mean, which multiplies the sum by the float 1/B (computed on the
+// host). A target element counts as set when it is non-zero, like
+// .to(torch.bool). TT: float or unsigned char (bool storage).
+constexpr int SUBSET_ACC_THREADS = 1024;
+
+template <typename TT>
+__global__ void subset_accuracy_kernel(const TT* __restrict__ target,
+                                       const unsigned char* __restrict__ pred,
+                                       float* __restrict__ out, int B, int C,
+                                       float inv_b) {
+    int cnt = 0;
+    for (int r = threadIdx.x; r < B; r += blockDim.x) {
+        const TT* t = target + (long)r * C;
+        const unsigned char* p = pred + (long)r * C;
+        bool all = true;
+        for (int c = 0; c < C; ++c)
+            all = all && ((t[c] != (TT)0) == (p[c] != 0));
+        cnt += all ? 1 : 0;
+    }
+    cnt += __shfl_xor(cnt, 1); cnt += __shfl_xor(cnt, 2);
+    cnt += __shfl_xor(cnt, 4); cnt += __shfl_xor(cnt, 8);
+    cnt += __shfl_xor(cnt, 16); cnt += __shfl_xor(cnt, 32);
+    __shared__ int red[SUBSET_ACC_THREADS / 64];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) total += red[w];
+        out[0] = (float)total * inv_b;
+    }
+}
+
+// ===========================================================================
 // normalize_table
 // ===========================================================================
 // y[n][f] = T((nan_to_num(x[n][f]) - xmin[f]) / (xmax[f] - xmin[f])): the
@@ -361,7 +612,6 @@ __global__ void normalize_table_kernel(const float* __restrict__ x,
 // then no vector straddles two windows and there is no tail. LB == 0 is the
 // element-wise path for everything else: a vector may straddle windows
 // (two unrelated source addresses) and the last one may be partial.
-struct alignas(16) chunk16 { unsigned int u[4]; };
 
 template <int LB>
 FMDA_DEV void load16(void* dst, const void* src) {
@@ -528,14 +778,118 @@ extern "C" int fmda_finalize_gru_wgrads_launch(
     return launch_ok();
 }
 
+// finalize_gru_wgrads in the order of the eager chunk sum. Both partials
+// have EAGER_SUM_CHUNKS chunks (the caller checks that, and the output
+// counts the order depends on).
+extern "C" int fmda_finalize_gru_wgrads_eager_launch(
+        int part_bf16, const void* part_ih, const void* part_hh,
+        float* const* grads, int D, int H, int Hp, int F,
+        hipStream_t stream) {
+    GruWgrads o = {};
+    for (int d = 0; d < D; ++d) {
+        o.dw_ih[d] = grads[2 * d + 0];
+        o.dw_hh[d] = grads[2 * d + 1];
+    }
+    const long total = (long)D * 3 * H * ((long)F + H);
+    // vectors of 4 when no vector can leave its row
+    const bool vec = H % 4 == 0 && F % 4 == 0;
+    const long threads = vec ? total / 4 : total;
+    const dim3 grid((unsigned)((threads + 255) / 256));
+#define FMDA_FIN(PT, V)                                                    \
+    finalize_gru_wgrads_eager_kernel<PT, V><<<grid, 256, 0, stream>>>(     \
+        (const PT*)part_ih, (const PT*)part_hh, o, D, H, Hp, F)
+    if (part_bf16) {
+        if (vec) FMDA_FIN(__hip_bfloat16, 4);
+        else FMDA_FIN(__hip_bfloat16, 1);
+    } else {
+        if (vec) FMDA_FIN(float, 4);
+        else FMDA_FIN(float, 1);
+    }
+#undef FMDA_FIN
+    return launch_ok();
+}
+
+extern "C" int fmda_eager_sum_chunks() { return EAGER_SUM_CHUNKS; }
+
+// parts: (EAGER_SUM_CHUNKS, C, K) in the compute dtype
+extern "C" int fmda_head_wgrads_eager_launch(
+        int is_bf16, const void* parts, const float* db_sum, float* dW,
+        float* db, int K, int C, hipStream_t stream) {
+    const int n_w = C * K;
+    const dim3 grid((n_w + C + 255) / 256);
+    if (is_bf16)
+        head_wgrads_eager_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
+            (const __hip_bfloat16*)parts, db_sum, dW, db, n_w, C);
+    else
+        head_wgrads_eager_kernel<float><<<grid, 256, 0, stream>>>(
+            (const float*)parts, db_sum, dW, db, n_w, C);
+    return launch_ok();
+}
+
+// target_is_float: fp32 target, else bool storage; pred: bool storage
+extern "C" int fmda_subset_accuracy_launch(
+        int target_is_float, const void* target, const void* pred,
+        float* out, int B, int C, hipStream_t stream) {
+    const float inv_b = 1.0f / (float)B;
+    if (target_is_float)
+        subset_accuracy_kernel<float><<<1, SUBSET_ACC_THREADS, 0, stream>>>(
+            (const float*)target, (const unsigned char*)pred, out, B, C,
+            inv_b);
+    else
+        subset_accuracy_kernel<unsigned char>
+            <<<1, SUBSET_ACC_THREADS, 0, stream>>>(
+                (const unsigned char*)target, (const unsigned char*)pred,
+                out, B, C, inv_b);
+    return launch_ok();
+}
+
+// Column tile KT of head_fwd_master_staged_kernel for these shapes: the
+// largest multiple of 8 (at most K) whose x and W tiles fit in 64 KB of LDS
+// next to each other, or 0 when the staged kernel does not apply (rows that
+// are not whole 16-byte vectors, an unaligned x, or no room for a tile).
+static int head_fwd_stage_tile(const void* x, int es, int B, int K, int C,
+                               int* rows_cap) {
+    const int V = 16 / es;
+    if (B < 1 || C < 1 || K % V != 0 || (uintptr_t)x % 16 != 0) return 0;
+    // a block's 256 consecutive (row, class) pairs touch at most this many
+    // rows
+    const int rc = 255 / C + 2 < B ? 255 / C + 2 : B;
+    // 1 KB short of 64 KB: the kernel's static LDS comes on top
+    const long budget = 64512 - 16L * rc - 16L * C;
+    long kt = budget / ((long)rc * es + 4L * C);
+    if (kt > K) kt = K;
+    if (kt < K) kt -= kt % 8;          // K itself is a multiple of V
+    *rows_cap = rc;
+    return kt >= 8 || kt == K ? (int)kt : 0;
+}
+
+// staged != 0: head_fwd_master_staged_kernel where it applies (same bits,
+// operands read through LDS); 0: always the direct kernel.
 extern "C" int fmda_head_fwd_master_launch(
         int is_bf16, const void* x, const float* W, const float* bias,
         const float* y, const float* wgt, const float* pw, float* logits,
-        float* sig, float* loss_sum, int B, int K, int C,
+        float* sig, float* loss_sum, int B, int K, int C, int staged,
         hipStream_t stream) {
     // same launch shape as fmda_head_fwd_launch: the per-block loss
     // partials (and their sum) must not change
     const dim3 grid((B * C + 255) / 256);
+    int rows_cap = 0;
+    const int es = is_bf16 ? 2 : 4;
+    const int kt = staged ? head_fwd_stage_tile(x, es, B, K, C, &rows_cap) : 0;
+    if (kt > 0) {
+        const size_t lds = (size_t)rows_cap * (kt * es + 16) +
+                           (size_t)C * (kt + 4) * 4;
+        if (is_bf16)
+            head_fwd_master_staged_kernel<__hip_bfloat16>
+                <<<grid, 256, lds, stream>>>(
+                    (const __hip_bfloat16*)x, W, bias, y, wgt, pw, logits,
+                    sig, loss_sum, B, K, C, kt, rows_cap);
+        else
+            head_fwd_master_staged_kernel<float><<<grid, 256, lds, stream>>>(
+                (const float*)x, W, bias, y, wgt, pw, logits, sig, loss_sum,
+                B, K, C, kt, rows_cap);
+        return launch_ok();
+    }
     if (is_bf16)
         head_fwd_master_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
             (const __hip_bfloat16*)x, W, bias, y, wgt, pw, logits, sig,
@@ -550,15 +904,18 @@ extern "C" int fmda_head_fwd_master_launch(
 extern "C" int fmda_head_bwd_master_launch(
         int is_bf16, const float* sig, const float* y, const float* wgt,
         const float* pw, const float* gscale, const float* W,
-        float* dlogits, void* dx, int B, int K, int C, hipStream_t stream) {
+        float* dlogits, void* dlogits_t, void* dx, int B, int K, int C,
+        hipStream_t stream) {
+    // dlogits_t: optional (B, C) copy of dlogits in the compute dtype
     const dim3 grid((B * K + 255) / 256);
     if (is_bf16)
         head_bwd_master_kernel<__hip_bfloat16><<<grid, 256, 0, stream>>>(
-            sig, y, wgt, pw, gscale, W, dlogits, (__hip_bfloat16*)dx, B, K,
-            C);
+            sig, y, wgt, pw, gscale, W, dlogits, (__hip_bfloat16*)dlogits_t,
+            (__hip_bfloat16*)dx, B, K, C);
     else
         head_bwd_master_kernel<float><<<grid, 256, 0, stream>>>(
-            sig, y, wgt, pw, gscale, W, dlogits, (float*)dx, B, K, C);
+            sig, y, wgt, pw, gscale, W, dlogits, (float*)dlogits_t,
+            (float*)dx, B, K, C);
     return launch_ok();
 }
 

@@ -18,7 +18,7 @@ import torch
 
 from . import load_extension
 from .blas import (chunked_colsum, chunked_outer, chunked_outer_parts,
-                   enable_tunableop)
+                   enable_tunableop, split_chunks)
 
 # Minimum padded hidden is 32: the bf16 recurrence tiles MFMA K=32, so
 # Hp=16 would give a ZERO-trip GEMM loop (caught by the randomized shape
@@ -37,9 +37,11 @@ def _glue_mode() -> int:
     """FMDA_NATIVE_GLUE, read per call:
     1 (default): weight packing, the head's read of the fp32 masters, the
        pooling casts and the pooled-head feature path (pooled_features) run
-       as single HIP kernels. Every one of these steps is exact, so a
-       training step computes what the eager formulation computes, bit for
-       bit.
+       as single HIP kernels; so do the split-K chunk sums of the GRU and
+       head weight grads where the kernels can follow the order of torch's
+       own sum (_eager_sum_known), and metrics.subset_accuracy. Every one
+       of these steps is exact, so a training step computes what the eager
+       formulation computes, bit for bit.
     2: also the weight-gradient reductions (finalize_gru_wgrads,
        head_wgrads). They sum in fp32 in their own fixed order, and the
        head's dW / db skip the round trip through bf16, so gradients differ
@@ -55,6 +57,16 @@ def _native_glue() -> bool:
 
 def _native_reductions() -> bool:
     return _glue_mode() == 2
+
+
+def _eager_sum_known(M: int, outputs: int) -> bool:
+    """Whether the native kernels can sum the split-K partials of an
+    (M, N)^T @ (M, K) chunked_outer with N*K = `outputs` exactly as
+    `parts.float().sum(dim=0)` does. That order is derived (and tested) for
+    ATen's 64 x 2 reduce block only: 64 chunks, at least 512 outputs, a
+    multiple of 4 (the extension's eager_sum_applies checks the same on
+    the partials). Everything else, ragged M included, stays eager."""
+    return split_chunks(M) == 64 and outputs >= 512 and outputs % 4 == 0
 
 
 def _fp32_cuda(*tensors) -> bool:
@@ -451,7 +463,7 @@ class _HeadLossMaster(torch.autograd.Function):
         x2d = x2d.contiguous()
         W = W.contiguous()
         y, wgt, pw = y.contiguous(), wgt.contiguous(), pw.contiguous()
-        logits, sig, loss_sum = ext.head_loss_fwd_master(
+        logits, sig, loss_sum, _ = ext.head_loss_fwd_master(
             x2d, W, b.contiguous(), y, wgt, pw)
         B, C = logits.shape
         loss = (loss_sum / float(B * C)).reshape(())
@@ -463,12 +475,23 @@ class _HeadLossMaster(torch.autograd.Function):
     def backward(ctx, dloss, _dlogits):
         ext = load_extension()
         x2d, W, y, wgt, pw, sig = ctx.saved_tensors
-        dlogits, dx = ext.head_loss_bwd_master(
-            sig, y, wgt, pw, dloss.reshape(1).float().contiguous(), W,
-            x2d.dtype)
+        gscale = dloss.reshape(1).float().contiguous()
         if ctx.native_reductions:
+            dlogits, dx = ext.head_loss_bwd_master(sig, y, wgt, pw, gscale,
+                                                   W, x2d.dtype)
             dW, db = ext.head_wgrads(dlogits, x2d)
+        elif _eager_sum_known(x2d.shape[0], W.numel()):
+            # the chain of the branch below in 4 launches: the kernel also
+            # emits dlogits.to(dtype), the split-K bmm stays the library's,
+            # and one kernel sums its partials in the eager sum's order and
+            # applies the two casts to dW and db. Same bits.
+            dlogits, dx, dl = ext.head_loss_bwd_master(
+                sig, y, wgt, pw, gscale, W, x2d.dtype, True)
+            dW, db = ext.head_wgrads_eager(chunked_outer_parts(dl, x2d),
+                                           dlogits.sum(dim=0))
         else:
+            dlogits, dx = ext.head_loss_bwd_master(sig, y, wgt, pw, gscale,
+                                                   W, x2d.dtype)
             # _HeadLoss.backward on the cast copies, then the cast-back of
             # W.to(dtype) / b.to(dtype): the same values, rounding included
             dW = chunked_outer(dlogits.to(x2d.dtype), x2d).to(W.dtype)
@@ -534,6 +557,7 @@ class _BiGRULayer(torch.autograd.Function):
         ctx.h0 = h0c
         ctx.meta = (D, H, Hp, out_drop_p, out_drop_seed)
         ctx.native_reductions = _native_reductions()
+        ctx.native_glue = _native_glue()
         ctx.set_materialize_grads(False)
         if len(res) > 2:
             return out, h_last, res[2]
@@ -581,6 +605,20 @@ class _BiGRULayer(torch.autograd.Function):
                 chunked_outer_parts(dgi.reshape(M, -1), x2d),
                 chunked_outer_parts(dgh.reshape(M, -1), out.reshape(M, -1)),
                 D, H, Hp)
+            wgrads = [(wg[2 * d], wg[2 * d + 1]) for d in range(D)]
+        elif (ctx.native_glue and dgh0 is None
+              and dgi.dtype in (torch.bfloat16, torch.float32)
+              and _eager_sum_known(M, D * 3 * Hp * x2d.shape[1])
+              and _eager_sum_known(M, D * 3 * Hp * D * Hp)):
+            # default mode: the same kernel shape, but the 64 chunks are
+            # summed in the order of the eager `parts.float().sum(dim=0)`
+            # below, so the four grads are the eager chain's bits: per
+            # layer 2 casts, 2 sums, D strided copies (and the unpadding
+            # copies) become one launch
+            wg = ext.finalize_gru_wgrads(
+                chunked_outer_parts(dgi.reshape(M, -1), x2d),
+                chunked_outer_parts(dgh.reshape(M, -1), out.reshape(M, -1)),
+                D, H, Hp, True)
             wgrads = [(wg[2 * d], wg[2 * d + 1]) for d in range(D)]
         else:
             # dW_hh via the time-shifted dGh and one split-K reduction (fp32
