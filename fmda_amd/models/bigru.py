@@ -123,16 +123,17 @@ class BiGRU(nn.Module):
         """forward_features from the already dropped input on: the GRU
         stack and the pooled concat."""
         if input_seq.is_cuda:
-            from ..ops.interface import (bigru_stack_raw, pooled_features,
+            from ..ops.interface import (bigru_stack_features,
                                          pooled_features_native)
             if pooled_features_native(input_seq, self.hidden_size):
                 # the whole feature path in one HIP kernel each way, from
                 # the top layer's raw fp32 final state: no h_n, no casts,
-                # no direction sum, no cats (same bits as _pool_concat)
-                gru_out, h_last = bigru_stack_raw(
+                # no direction sum, no cats (same bits as _pool_concat);
+                # in training the top layer's BPTT kernel builds its d_out
+                # from the feature gradient itself (fused_pool_bwd_native)
+                return bigru_stack_features(
                     input_seq, self.gru, self.n_layers, self.bidirectional,
                     self.dropout_p, self.training, hidden)
-                return pooled_features(gru_out, h_last)
             gru_out, h_n = self._gru_hip(input_seq, hidden)
         else:
             gru_out, h_n = self.gru(input_seq, hidden)

@@ -43,6 +43,15 @@ extern "C" int fmda_gru_bwd_launch(int is_bf16, int Hp, const void* gi,
                                    unsigned long long drop_seed,
                                    const float* h0, void* dgh0,
                                    hipStream_t stream);
+extern "C" int fmda_gru_bwd_pooled_available();
+extern "C" int fmda_gru_bwd_pooled_launch(const void* gi, const void* w,
+                                          const void* wt, const float* bhh,
+                                          const void* out, const void* dfeat,
+                                          const int* amax, long ld, void* dgi,
+                                          void* dgh, float* dh0, float* dbhh,
+                                          int B, int Tseq, int n_dir,
+                                          const float* h0, void* dgh0,
+                                          hipStream_t stream);
 extern "C" int fmda_mfma_selftest_launch(const void* A, const void* Bm,
                                          float* C, hipStream_t stream);
 extern "C" int fmda_pool_fwd_launch(int is_bf16, const void* out, void* maxv,
@@ -324,15 +333,68 @@ std::vector<torch::Tensor> gru_fwd_windows(torch::Tensor gi_rows,
                             is_bf16, stride * row, c10::nullopt, 0.0, 0);
 }
 
+// dout (B, T, n_dir*Hp) and dhT (n_dir, B, Hp) fp32 are the layer's output
+// gradients. A top layer whose out feeds pool_features_fwd alone passes
+// dfeat (B, 3Hp) bf16 and amax (B, Hp) int32 instead (dout = dhT = None):
+// the kernel then synthesises what pool_features_bwd would have written.
 std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
                                    torch::Tensor bhh, torch::Tensor out,
-                                   torch::Tensor dout, torch::Tensor dhT,
+                                   c10::optional<torch::Tensor> dout_opt,
+                                   c10::optional<torch::Tensor> dhT_opt,
                                    double drop_p, int64_t drop_seed,
                                    c10::optional<torch::Tensor> h0_opt,
-                                   c10::optional<torch::Tensor> wt_opt) {
+                                   c10::optional<torch::Tensor> wt_opt,
+                                   c10::optional<torch::Tensor> dfeat_opt,
+                                   c10::optional<torch::Tensor> amax_opt) {
     int B, T, n_dir, Hp;
     bool is_bf16;
     check_common(gi, w, bhh, B, T, n_dir, Hp, is_bf16);
+    const bool pooled = dfeat_opt.has_value() || amax_opt.has_value();
+    torch::Tensor dout, dhT, dfeat, amax;
+    long dfeat_ld = 0;
+    if (pooled) {
+        TORCH_CHECK(dfeat_opt.has_value() && amax_opt.has_value() &&
+                    !dout_opt.has_value() && !dhT_opt.has_value(),
+                    "fmda gru_bwd: pass either (dout, dhT) or (dfeat, amax)");
+        dfeat = dfeat_opt.value();
+        amax = amax_opt.value();
+        TORCH_CHECK(is_bf16 && Hp == 128,
+                    "fmda gru_bwd: the pooled path needs bf16 and "
+                    "H == Hp == 128, got Hp=", Hp);
+        TORCH_CHECK(T <= 256, "fmda gru_bwd: the pooled path keeps amax in "
+                    "one byte, T=", T, " > 256");
+        TORCH_CHECK(drop_p == 0.0,
+                    "fmda gru_bwd: the pooled path has no dropout");
+        TORCH_CHECK(fmda_gru_bwd_pooled_available() == 1,
+                    "fmda gru_bwd: no pooled variant of the kernel selected "
+                    "by FMDA_BWD_BT16 / FMDA_BWD_PHASES");
+        TORCH_CHECK(dfeat.is_cuda() && dfeat.dim() == 2 &&
+                    dfeat.scalar_type() == torch::kBFloat16 &&
+                    dfeat.size(0) == B && dfeat.size(1) == 3 * Hp,
+                    "fmda gru_bwd: dfeat must be bf16 (B, 3H) on the GPU");
+        TORCH_CHECK(amax.is_cuda() && amax.is_contiguous() &&
+                    amax.scalar_type() == torch::kInt32 && amax.dim() == 2 &&
+                    amax.size(0) == B && amax.size(1) == Hp,
+                    "fmda gru_bwd: amax must be contiguous int32 (B, H)");
+        TORCH_CHECK(dfeat.stride(1) == 1,
+                    "fmda gru_bwd: dfeat needs unit column stride");
+        dfeat_ld = B == 1 ? 3L * Hp : (long)dfeat.stride(0);
+        // 16-byte row loads: whole 8-element groups on an aligned base
+        TORCH_CHECK(dfeat_ld >= 3 * Hp && dfeat_ld % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(dfeat.data_ptr()) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(amax.data_ptr()) % 16 == 0,
+                    "fmda gru_bwd: dfeat needs a row pitch >= 3H that is a "
+                    "multiple of 8 and 16-byte aligned data");
+        TORCH_CHECK(out.is_cuda() && out.scalar_type() == gi.scalar_type() &&
+                    out.dim() == 3 && out.size(0) == B && out.size(1) == T &&
+                    out.size(2) == (int64_t)n_dir * Hp,
+                    "fmda gru_bwd: out must be (B, T, n_dir*Hp)");
+    } else {
+        TORCH_CHECK(dout_opt.has_value() && dhT_opt.has_value(),
+                    "fmda gru_bwd: dout and dhT are required");
+        dout = dout_opt.value();
+        dhT = dhT_opt.value();
+    }
     const float* h0 = nullptr;
     torch::Tensor dgh0;
     void* dgh0_ptr = nullptr;
@@ -346,9 +408,11 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
         dgh0 = torch::empty({n_dir, B, (int64_t)3 * Hp}, gi.options());
         dgh0_ptr = dgh0.data_ptr();
     }
-    TORCH_CHECK(out.is_contiguous() && dout.is_contiguous() &&
-                dhT.is_contiguous(), "fmda gru_bwd: tensors must be contiguous");
-    TORCH_CHECK(dhT.scalar_type() == torch::kFloat32, "dhT must be fp32");
+    TORCH_CHECK(out.is_contiguous() &&
+                (pooled || (dout.is_contiguous() && dhT.is_contiguous())),
+                "fmda gru_bwd: tensors must be contiguous");
+    TORCH_CHECK(pooled || dhT.scalar_type() == torch::kFloat32,
+                "dhT must be fp32");
     // fp32 BPTT at Hp=512 needs ~264 KB of LDS staging — architecturally
     // out of budget (160 KB/CU); bf16 (the training dtype) covers H>256.
     TORCH_CHECK(is_bf16 || Hp <= 256,
@@ -408,7 +472,15 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor gi, torch::Tensor w,
     // quantizes EXACTLY like the forward paths, so the recomputed backward
     // mask can never disagree with the forward one at a rounding boundary.
     const DropParams dp = drop_params(drop_p);
-    if (column_split) {
+    if (pooled) {
+        TORCH_CHECK(wt_ptr != nullptr, "fmda gru_bwd: pooled path needs wt");
+        rc = fmda_gru_bwd_pooled_launch(
+            gi.data_ptr(), w.data_ptr(), wt_ptr, bhh.data_ptr<float>(),
+            out.data_ptr(), dfeat.data_ptr(), amax.data_ptr<int>(), dfeat_ld,
+            dgi.data_ptr(), dgh.data_ptr(), dh0.data_ptr<float>(),
+            dbpart.data_ptr<float>(), B, T, n_dir, h0, dgh0_ptr,
+            stream.stream());
+    } else if (column_split) {
         const unsigned int cs_thr = dp.thr;
         const float cs_scale = dp.scale;
         const int BR = 256;
@@ -1105,7 +1177,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("gi"), py::arg("w"), py::arg("bhh"), py::arg("out"),
           py::arg("dout"), py::arg("dhT"), py::arg("drop_p") = 0.0,
           py::arg("drop_seed") = 0, py::arg("h0") = py::none(),
-          py::arg("wt") = py::none());
+          py::arg("wt") = py::none(), py::arg("dfeat") = py::none(),
+          py::arg("amax") = py::none());
+    m.def("gru_bwd_pooled_available",
+          []() { return fmda_gru_bwd_pooled_available() == 1; },
+          "whether gru_bwd(dfeat=, amax=) has a kernel in this process");
     m.def("mfma_selftest", &mfma_selftest, "mfma fragment layout self-test");
     m.def("dropout_fused", &dropout_fused,
           "counter-based dropout (mask recomputed in backward)");

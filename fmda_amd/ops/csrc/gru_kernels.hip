@@ -1348,7 +1348,27 @@ void gru_fwd_b1_kernel(const __hip_bfloat16* __restrict__ gi,
 // 4 = carry GEMM). Production uses 7; other masks exist only so
 // scripts/kernel_micro.py can time each phase's contribution to the
 // serial chain by differencing (outputs are garbage for masks != 7).
-template <int BT, int Hp, int NT, int WPE, int PHASES = 7>
+//
+// POOLED: the layer feeds pool_features_fwd and nothing else, so its d_out
+// is never materialised. pool_features_bwd_kernel would write
+//   d_out[b, t, d*H + j] = bf16(ga + (t == amax[b, j] ? gm : 0.0f))
+// with ga = float(dfeat[b, 2H + j]) / (float)T, gm = float(dfeat[b, H + j])
+// for both directions, and d_hlast[d, b, j] = float(dfeat[b, j]). Here the
+// block builds, once, a table of (v0 = bf16(ga + 0.0f), v1 = bf16(ga + gm),
+// amax as a byte: T <= 256) for its BT rows in the LDS that the two d_out
+// tiles occupied, and every step picks v1 at t == amax and v0 elsewhere:
+// the same bits, without the (B, T, D*H) write, its read back, and the
+// glds_do DMA stream. dout / dhT are not read (the launcher passes null);
+// dfeat / amax / dfeat_ld are not read when !POOLED. No dropout in this
+// variant (the top layer never defers one): that branch is compiled out.
+//
+// Table layout: entry k of thread `tid` (k = (i * MT + m) * 4 + e, the
+// thread's own C elements in the order phase B visits them) sits at word
+// k * NT + tid of pv_s (v0 low half, v1 high half) and at byte e of word
+// (i * MT + m) * NT + tid of im_s: consecutive lanes read consecutive
+// words, and the offsets of k are immediates off one base register.
+template <int BT, int Hp, int NT, int WPE, int PHASES = 7,
+          bool POOLED = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                           amdgpu_waves_per_eu(WPE, WPE)))
 void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
@@ -1364,7 +1384,9 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
                        unsigned int drop_thr, float drop_scale,
                        unsigned long long drop_seed,
                        const float* __restrict__ h0,
-                       __hip_bfloat16* __restrict__ dgh0) {
+                       __hip_bfloat16* __restrict__ dgh0,
+                       const __hip_bfloat16* __restrict__ dfeat,
+                       const int* __restrict__ amax, long dfeat_ld) {
     constexpr int NW = NT / 64;
     constexpr int MT = BT / 16;
     constexpr int NCT = Hp / 16;
@@ -1400,8 +1422,13 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
     __hip_bfloat16* gi_s2 = (__hip_bfloat16*)p; p += 2 * BT * GP;
     __hip_bfloat16* hb_s0 = (__hip_bfloat16*)p; p += BT * HROW;
     __hip_bfloat16* hb_s1 = (__hip_bfloat16*)p; p += BT * HROW;
-    __hip_bfloat16* do_s0 = (__hip_bfloat16*)p; p += BT * HROW;
+    // dense: two d_out tiles (2 * BT * HROW bytes); pooled: the (v0, v1)
+    // words in exactly that space, then BT * Hp amax bytes
+    __hip_bfloat16* do_s0 = (__hip_bfloat16*)p;
+    unsigned int* pv_s = (unsigned int*)p; p += BT * HROW;
     __hip_bfloat16* do_s1 = (__hip_bfloat16*)p; p += BT * HROW;
+    unsigned int* im_s = (unsigned int*)p;
+    if (POOLED) p += BT * Hp;
     __hip_bfloat16* dgh_s0 = (__hip_bfloat16*)p; p += 2 * BT * GP3;
     __hip_bfloat16* dgh_s1 = (__hip_bfloat16*)p; p += 2 * BT * GP3;
     float* bhh_s = (float*)p;
@@ -1422,6 +1449,67 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
 
     for (int c = tid; c < 3 * Hp; c += NT)
         bhh_s[c] = bhh[(long)dir * 3 * Hp + c];
+
+    if (POOLED) {
+        // Table fill, before any glds like the loads below: one (row,
+        // 8-column group) per thread and pass, three 16-byte dfeat loads
+        // and two 16-byte amax loads per lane, scattered to the owners'
+        // slots. ga, gm and the roundings are pool_features_bwd_kernel's
+        // expressions (`+ 0.0f` turns a -0.0 average gradient into +0.0).
+        // The bf16 d_hlast column goes to dgh_s0 in the same [k][tid]
+        // order; nothing else touches dgh_s0 before the first phase B,
+        // which runs after the prologue barrier below.
+        constexpr int H8 = Hp / 8;
+        unsigned short* gl_s = (unsigned short*)dgh_s0;
+        for (int c = tid; c < BT * H8; c += NT) {
+            const int b = c / H8;
+            const int h8 = (c % H8) * 8;
+            bf16x8_t dl, dm, da;
+            int4 a0 = make_int4(0, 0, 0, 0), a1 = a0;
+            const bool rowlive = (b < rows_valid);
+            if (rowlive) {
+                const __hip_bfloat16* dr =
+                    dfeat + (long)(b0 + b) * dfeat_ld + h8;
+                dl = *(const bf16x8_t*)dr;
+                dm = *(const bf16x8_t*)(dr + Hp);
+                da = *(const bf16x8_t*)(dr + 2 * Hp);
+                const int* ai = amax + (long)(b0 + b) * Hp + h8;
+                a0 = *(const int4*)ai;
+                a1 = *(const int4*)(ai + 4);
+            }
+            const int imv[8] = {a0.x, a0.y, a0.z, a0.w,
+                                a1.x, a1.y, a1.z, a1.w};
+            // owner of (b, j): column tile ct = j / 16 -> wave ct % NW,
+            // i = ct / NW; lane (j & 15) + 16 * ((b >> 2) & 3); m = b / 16;
+            // e = b & 3 (the C layout of the MFMA, see phase B)
+            const int ct = h8 >> 4;             // 8 columns: one column tile
+            const int im0 = (ct / NW) * MT + (b >> 4);
+            const int e = b & 3;
+            const int t0 = (ct % NW) * 64 + 16 * ((b >> 2) & 3) + (h8 & 15);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                unsigned int pv = 0u, iv = 0u;
+                unsigned short gl = 0;
+                if (rowlive) {
+                    const float ga = (float)da[k] / (float)Tseq;
+                    const float gm = (float)dm[k];
+                    const __bf16 v0 = (__bf16)__float2bfloat16(ga + 0.0f);
+                    const __bf16 v1 = (__bf16)__float2bfloat16(ga + gm);
+                    pv = (unsigned int)__builtin_bit_cast(unsigned short, v0) |
+                         ((unsigned int)__builtin_bit_cast(unsigned short, v1)
+                          << 16);
+                    iv = (unsigned int)imv[k];
+                    gl = __builtin_bit_cast(unsigned short, (__bf16)dl[k]);
+                }
+                pv_s[(im0 * 4 + e) * NT + t0 + k] = pv;
+                ((unsigned char*)im_s)[(im0 * NT + t0 + k) * 4 + e] =
+                    (unsigned char)iv;
+                gl_s[(im0 * 4 + e) * NT + t0 + k] = gl;
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    }
 
     // Both W fragment sets, register-resident; loaded ONCE here (ordinary
     // loads are legal before any glds is issued).
@@ -1460,8 +1548,16 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int b = 16 * m + 4 * (lane >> 4) + e;
-                dhreg[i][m][e] =
-                    (b < rows_valid) ? hT[(long)b * Hp + j] : 0.0f;
+                if (POOLED) {
+                    // float(dfeat[b, j]) for both directions, as the pool
+                    // backward wrote d_hlast; dead rows were filled with 0
+                    const unsigned short gl = ((const unsigned short*)
+                        dgh_s0)[((i * MT + m) * 4 + e) * NT + tid];
+                    dhreg[i][m][e] = __uint_as_float((unsigned int)gl << 16);
+                } else {
+                    dhreg[i][m][e] =
+                        (b < rows_valid) ? hT[(long)b * Hp + j] : 0.0f;
+                }
             }
     }
 
@@ -1543,7 +1639,7 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
         const int u = Tseq - 1;
         const int tt = rev ? 0 : u;
         glds_gi(tt, u % 3);
-        glds_do(tt, u & 1);
+        if (!POOLED) glds_do(tt, u & 1);
         if (u > 0) {
             const int ttp = rev ? 1 : (u - 1);
             glds_hb(ttp, u & 1);
@@ -1566,7 +1662,7 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
         if (have_next) {
             const int ttn = rev ? (Tseq - u) : (u - 1);
             glds_gi(ttn, (u - 1) % 3);
-            glds_do(ttn, 1 - q);
+            if (!POOLED) glds_do(ttn, 1 - q);
             if (u >= 2)
                 glds_hb(rev ? (Tseq + 1 - u) : (u - 2), 1 - q);
             else
@@ -1626,6 +1722,11 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
             const __bf16* dorow = (const __bf16*)do_buf(q);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
+                // this thread's four amax bytes of (i, m); read every step
+                // like the (v0, v1) words below (the table stays in LDS:
+                // the kernel has no registers to spare for it)
+                unsigned int imw = 0u;
+                if (POOLED) imw = im_s[(i * MT + m) * NT + tid];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int b = 16 * m + 4 * (lane >> 4) + e;
@@ -1640,8 +1741,19 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
                     const float z = sigmoidf(iz + gz);
                     const float n = fast_tanh(in_ + r * hn);
                     const float hprev = hb_read(hbq, b, j);
-                    float doval = live ? (float)dorow[b * Hp + j] : 0.0f;
-                    if (drop_thr != 0u) {
+                    float doval;
+                    if (POOLED) {
+                        const unsigned int pv =
+                            pv_s[((i * MT + m) * 4 + e) * NT + tid];
+                        const int im = (int)((imw >> (8 * e)) & 0xFFu);
+                        // bf16 -> fp32: v1 is the high half already
+                        const unsigned int bits =
+                            (tt == im) ? (pv & 0xFFFF0000u) : (pv << 16);
+                        doval = live ? __uint_as_float(bits) : 0.0f;
+                    } else {
+                        doval = live ? (float)dorow[b * Hp + j] : 0.0f;
+                    }
+                    if (!POOLED && drop_thr != 0u) {
                         // fused inter-layer dropout backward: dout is the
                         // grad w.r.t. the DROPPED activations; recompute
                         // the counter-based mask (same splitmix64 draw as
@@ -1688,6 +1800,14 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
         // counted form assumes every thread issued its full store quota;
         // in the (single) batch-tail block dead rows skip stores, so that
         // block full-drains instead — exactness over speed there.
+        // POOLED: a thread's vector-memory operations of a step are, in
+        // program order, the gi DMAs, the h DMA (or zero_hb's h0 loads)
+        // and then the NST tile stores; the variant only takes the d_out
+        // DMA out from between them, and its table reads are LDS traffic
+        // (lgkmcnt). The NST stores are therefore still the youngest NST
+        // operations of every thread of a full block, vmcnt(NST) still
+        // means "every DMA of this step has landed", and the tail block
+        // still drains to zero.
         if (have_next) {
             if (have_prev && rows_valid == BT)
                 asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NST) : "memory");
@@ -3589,7 +3709,39 @@ static int launch_bwd_v3_128_t(const void* gi, const void* w, const void* wt,
         (const __hip_bfloat16*)out, (const __hip_bfloat16*)dout, dhT,
         (__hip_bfloat16*)dgi, (__hip_bfloat16*)dgh, dh0, dbhh, B, Tseq,
         n_dir, drop_thr, drop_scale, drop_seed, h0,
-        (__hip_bfloat16*)dgh0);
+        (__hip_bfloat16*)dgh0, nullptr, nullptr, 0L);
+    return 0;
+}
+
+// The POOLED variant of the BT=32 / NT=512 kernel: d_out and d_hlast come
+// from dfeat (row pitch ld elements) and amax inside the kernel. The two
+// 8 KB d_out tiles give way to the 16 KB + 4 KB table.
+static int launch_bwd_v3_128_pooled(const void* gi, const void* w,
+                                    const void* wt, const float* bhh,
+                                    const void* out, const void* dfeat,
+                                    const int* amax, long ld, void* dgi,
+                                    void* dgh, float* dh0, float* dbhh,
+                                    int B, int Tseq, int n_dir,
+                                    const float* h0, void* dgh0,
+                                    hipStream_t stream) {
+    constexpr int Hp = 128, BT = 32, NT = 512;
+    const size_t lds = 3 * 2 * BT * 3 * Hp + 2 * 2 * BT * Hp +
+                       (4 * BT * Hp + BT * Hp) + 2 * 2 * BT * (3 * Hp + 8) +
+                       4 * 3 * Hp;
+    static_assert(3 * 2 * BT * 3 * Hp + 2 * 2 * BT * Hp + 5 * BT * Hp +
+                  2 * 2 * BT * (3 * Hp + 8) + 4 * 3 * Hp <= 160 * 1024,
+                  "pooled table does not fit the LDS");
+    auto k = gru_bwd_v3_kernel<BT, Hp, NT, 2, 7, true>;
+    (void)hipFuncSetAttribute((const void*)k,
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const dim3 grid((B + BT - 1) / BT, n_dir);
+    k<<<grid, NT, lds, stream>>>(
+        (const __hip_bfloat16*)gi, (const __hip_bfloat16*)w,
+        (const __hip_bfloat16*)wt, bhh,
+        (const __hip_bfloat16*)out, nullptr, nullptr,
+        (__hip_bfloat16*)dgi, (__hip_bfloat16*)dgh, dh0, dbhh, B, Tseq,
+        n_dir, 0u, 1.0f, 0ull, h0, (__hip_bfloat16*)dgh0,
+        (const __hip_bfloat16*)dfeat, amax, ld);
     return 0;
 }
 
@@ -3844,6 +3996,33 @@ extern "C" int fmda_gru_bwd_launch(int is_bf16, int Hp, const void* gi,
         }
     }
 #undef G
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// Whether this process launches the kernel that has a POOLED variant (the
+// v3 BT=32 / NT=512 one): not under the FMDA_BWD_BT16 / FMDA_BWD_PHASES
+// A/B switches, which are latched once per process like the launcher's.
+extern "C" int fmda_gru_bwd_pooled_available() {
+    static const bool phases = getenv("FMDA_BWD_PHASES") != nullptr;
+    return (bwd_v3_bt16() || phases) ? 0 : 1;
+}
+
+// Backward of a bf16 Hp=128 layer whose out feeds pool_features_fwd alone:
+// d_out / d_hlast are synthesised in the kernel from dfeat (B, 3Hp) with
+// row pitch ld (elements, a multiple of 8 on a 16-byte aligned base) and
+// amax (B, Hp). One byte per amax entry: Tseq <= 256. No dropout.
+extern "C" int fmda_gru_bwd_pooled_launch(const void* gi, const void* w,
+                                          const void* wt, const float* bhh,
+                                          const void* out, const void* dfeat,
+                                          const int* amax, long ld, void* dgi,
+                                          void* dgh, float* dh0, float* dbhh,
+                                          int B, int Tseq, int n_dir,
+                                          const float* h0, void* dgh0,
+                                          hipStream_t stream) {
+    if (!fmda_gru_bwd_pooled_available()) return -8;
+    if (Tseq < 1 || Tseq > 256 || ld < 3 * 128 || ld % 8 != 0) return -9;
+    launch_bwd_v3_128_pooled(gi, w, wt, bhh, out, dfeat, amax, ld, dgi, dgh,
+                             dh0, dbhh, B, Tseq, n_dir, h0, dgh0, stream);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -371,27 +371,48 @@ class _PooledFeatures(torch.autograd.Function):
     bf16 = [dirsum(h_last) | max_T | avg_T], one kernel each way. Forward
     and backward give the bits of the chain they replace: the h_n cast,
     hidden_v[-1].sum(0), dirsum_pool, torch.cat and their autograd
-    (d_hlast = float(dfeat[:, :H]) for every direction)."""
+    (d_hlast = float(dfeat[:, :H]) for every direction).
+
+    Second form, apply(None, None, *layer) with `layer` the inputs of the
+    top _BiGRULayer (x, Hp, the eight masters, h0): that layer and the
+    pooling as one node. The forward runs the same kernels; in the backward
+    gru_bwd builds d_out and d_hlast from (dfeat, amax) in its own prologue
+    instead of reading the (B, T, D*H) tensor pool_features_bwd would have
+    written (fused_pool_bwd_native). Every bit stays what the two nodes
+    compute."""
 
     @staticmethod
-    def forward(ctx, out, h_last):
+    def forward(ctx, out, h_last, *layer):
         ext = load_extension()
+        saved = ()
+        ctx.fused = bool(layer)
+        if layer:
+            (out, h_last), saved = _BiGRULayer.run_forward(
+                ctx, *layer[:10], 0.0, 0, layer[10])
         feat, amax = ext.pool_features_fwd(out.contiguous(),
                                            h_last.contiguous())
-        ctx.save_for_backward(amax)
-        ctx.meta = (out.shape[1], h_last.shape[0])
+        ctx.save_for_backward(*saved, amax)
+        ctx.pool_meta = (out.shape[1], h_last.shape[0])
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
         ext = load_extension()
-        (amax,) = ctx.saved_tensors
-        T, n_dir = ctx.meta
+        *saved, amax = ctx.saved_tensors
+        T, n_dir = ctx.pool_meta
+        # the fused kernel loads dfeat rows in 16-byte pieces
         if (dfeat.dtype != torch.bfloat16 or dfeat.stride(1) != 1
-                or dfeat.stride(0) < dfeat.shape[1]):
+                or dfeat.stride(0) < dfeat.shape[1]
+                or (ctx.fused and dfeat.stride(0) % 8 != 0)):
             dfeat = dfeat.to(torch.bfloat16).contiguous()
-        d_out, d_hlast = ext.pool_features_bwd(dfeat, amax, T, n_dir)
-        return d_out, d_hlast
+        if not ctx.fused:
+            d_out, d_hlast = ext.pool_features_bwd(dfeat, amax, T, n_dir)
+            return d_out, d_hlast
+        if dfeat.data_ptr() % 16 != 0:
+            dfeat = dfeat.clone(memory_format=torch.contiguous_format)
+        g = _BiGRULayer.run_backward(ctx, tuple(saved), None, None,
+                                     dfeat=dfeat, amax=amax, x_index=2)
+        return (None, None) + g[:10] + (g[12],)
 
 
 # fmda_pool_fwd_launch gives grids below this many column pairs to the
@@ -530,6 +551,18 @@ class _BiGRULayer(torch.autograd.Function):
     def forward(ctx, x, Hp, w_ih0, w_hh0, b_ih0, b_hh0,
                 w_ih1, w_hh1, b_ih1, b_hh1, out_drop_p=0.0,
                 out_drop_seed=0, h0=None):
+        res, saved = _BiGRULayer.run_forward(
+            ctx, x, Hp, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1,
+            b_hh1, out_drop_p, out_drop_seed, h0)
+        ctx.save_for_backward(*saved)
+        return res
+
+    @staticmethod
+    def run_forward(ctx, x, Hp, w_ih0, w_hh0, b_ih0, b_hh0,
+                    w_ih1, w_hh1, b_ih1, b_hh1, out_drop_p, out_drop_seed,
+                    h0):
+        """The layer's forward for this node and _PooledFeatures: returns
+        (outputs, tensors to save); the caller saves them."""
         ext = load_extension()
         D = 2 if w_ih1 is not None else 1
         H = w_hh0.shape[1]
@@ -553,22 +586,35 @@ class _BiGRULayer(torch.autograd.Function):
         res = ext.gru_fwd(gi, w_hh_cat, b_hh_cat, h0c, out_drop_p,
                           out_drop_seed)
         out, h_last = res[0], res[1]
-        ctx.save_for_backward(x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out, wt)
+        saved = (x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out, wt)
         ctx.h0 = h0c
         ctx.meta = (D, H, Hp, out_drop_p, out_drop_seed)
         ctx.native_reductions = _native_reductions()
         ctx.native_glue = _native_glue()
         ctx.set_materialize_grads(False)
         if len(res) > 2:
-            return out, h_last, res[2]
-        return out, h_last
+            return (out, h_last, res[2]), saved
+        return (out, h_last), saved
 
     @staticmethod
     def backward(ctx, d_out, d_hlast, d_outdrop=None):
+        return _BiGRULayer.run_backward(ctx, ctx.saved_tensors, d_out,
+                                        d_hlast, d_outdrop)
+
+    @staticmethod
+    def run_backward(ctx, saved, d_out, d_hlast, d_outdrop=None,
+                     dfeat=None, amax=None, x_index=0):
+        """The layer's backward from (d_out, d_hlast), or from the pooled
+        head's (dfeat, amax), which gru_bwd turns into both itself (the
+        second form of _PooledFeatures, where x is input `x_index`)."""
         ext = load_extension()
-        x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out, wt = ctx.saved_tensors
+        x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out, wt = saved
         D, H, Hp, drop_p, drop_seed = ctx.meta
-        need_dx = ctx.needs_input_grad[0]
+        need_dx = ctx.needs_input_grad[x_index]
+        if dfeat is not None:
+            res = ext.gru_bwd(gi, w_hh_cat, b_hh_cat, out, None, None,
+                              0.0, 0, ctx.h0, wt, dfeat, amax)
+            return _BiGRULayer.finish_backward(ctx, saved, res, need_dx)
         if drop_p > 0:
             # the raw `out` output feeds nothing downstream when the fused
             # dropout path is active (h_n comes from h_last; the layer
@@ -586,6 +632,15 @@ class _BiGRULayer(torch.autograd.Function):
         # wt (from the native pack) spares gru_bwd its own transpose
         res = ext.gru_bwd(gi, w_hh_cat, b_hh_cat, out, d_out, d_hlast,
                           drop_p, drop_seed, h0c, wt)
+        return _BiGRULayer.finish_backward(ctx, saved, res, need_dx)
+
+    @staticmethod
+    def finish_backward(ctx, saved, res, need_dx):
+        """dx and the weight / bias gradients from gru_bwd's outputs."""
+        ext = load_extension()
+        x2d, w_ih_cat, w_hh_cat, b_hh_cat, gi, out, wt = saved
+        D, H, Hp, _, _ = ctx.meta
+        h0c = ctx.h0
         dgi, dgh, dh0_out, dbhh, dbih = res[:5]
         dgh0 = res[5] if len(res) > 5 else None
         M = dgi.shape[0] * dgi.shape[1]
@@ -650,6 +705,25 @@ class _BiGRULayer(torch.autograd.Function):
         (a0, b0, c0, e0), (a1, b1, c1, e1) = grads
         return (dx, None, a0, b0, c0, e0, a1, b1, c1, e1, None, None,
                 dh0_grad)
+
+
+def _fused_pool_bwd() -> bool:
+    """FMDA_FUSED_POOL_BWD, read per call like FMDA_NATIVE_GLUE: 0 keeps the
+    top layer and the pooled features two autograd nodes, with d_out
+    written by pool_features_bwd and read back by gru_bwd (A/B runs)."""
+    return os.environ.get("FMDA_FUSED_POOL_BWD", "1") != "0"
+
+
+def fused_pool_bwd_native(x: torch.Tensor, H: int) -> bool:
+    """Whether the top layer of a stack fed x (B, T, F) and its pooled
+    features run as one node (_PooledFeatures' second form): the
+    pooled_features_native
+    conditions, H == Hp == 128, T <= 256 (amax travels as one byte),
+    training with grad enabled, the switch on, and the BPTT kernel that
+    has the variant selected."""
+    return (_fused_pool_bwd() and pooled_features_native(x, H)
+            and H == 128 and x.shape[1] <= 256 and torch.is_grad_enabled()
+            and load_extension().gru_bwd_pooled_available())
 
 
 
@@ -739,13 +813,31 @@ def bigru_stack_raw(x: torch.Tensor, gru_module: torch.nn.GRU, n_layers: int,
     return out, h_last
 
 
+def bigru_stack_features(x: torch.Tensor, gru_module: torch.nn.GRU,
+                         n_layers: int, bidirectional: bool,
+                         dropout_p: float, training: bool,
+                         hidden: Optional[torch.Tensor] = None
+                         ) -> torch.Tensor:
+    """pooled_features(*bigru_stack_raw(...)) for a caller that holds
+    pooled_features_native(x, H): the (B, 3H) features alone. Where
+    fused_pool_bwd_native holds too, the top layer and the pooling are one
+    autograd node and d_out is never materialised."""
+    feat, _, _ = _bigru_stack(x, gru_module, n_layers, bidirectional,
+                              dropout_p, training, hidden, need_h_n=False,
+                              pooled=True)
+    return feat
+
+
 def _bigru_stack(x, gru_module, n_layers, bidirectional, dropout_p, training,
-                 hidden=None, need_h_n=True):
-    """(out, h_n or None, raw fp32 h_last of the top layer)."""
+                 hidden=None, need_h_n=True, pooled=False):
+    """(out, h_n or None, raw fp32 h_last of the top layer); with `pooled`
+    (pooled features, None, None)."""
     enable_tunableop()
     D = 2 if bidirectional else 1
     H = gru_module.hidden_size
     Hp = _pad_h(H)
+    assert not (pooled and need_h_n)
+    fuse_top = pooled and fused_pool_bwd_native(x, H)
 
     h0_layers = [None] * n_layers
     if hidden is not None:
@@ -781,6 +873,10 @@ def _bigru_stack(x, gru_module, n_layers, bidirectional, dropout_p, training,
         if not training and not torch.is_grad_enabled():
             out_pad, h_last = _infer_layer(gru_module, layer, p, Hp, H, inp,
                                            h0_l)
+        elif fuse_top and training and layer == n_layers - 1:
+            p1 = p[1] if D == 2 else (None, None, None, None)
+            return (_PooledFeatures.apply(None, None, inp, Hp, *p[0], *p1,
+                                          h0_l), None, None)
         elif D == 2:
             res = _BiGRULayer.apply(inp, Hp, *p[0], *p[1], *dp, h0_l)
             out_pad, h_last = res[0], res[1]
@@ -803,6 +899,8 @@ def _bigru_stack(x, gru_module, n_layers, bidirectional, dropout_p, training,
             else:
                 inp = fused_dropout(inp, dropout_p)
 
+    if pooled:
+        return pooled_features(inp, h_last), None, None
     h_n = torch.cat(h_n_parts, dim=0) if need_h_n else None  # (L*D, B, H)
     return inp, h_n, h_last
 
