@@ -85,6 +85,14 @@ extern "C" int fmda_spatial_dropout_launch(int is_bf16, const void* x,
 extern "C" int fmda_ingest_row_launch(void* ring, const float* row,
                                       const float* xmin, const float* xrng,
                                       int Tseq, int F, hipStream_t stream);
+extern "C" int fmda_ingest_rows_launch(void* rings, const float* rows,
+                                       const int* active, const float* xmin,
+                                       const float* xrng, int S, int Tseq,
+                                       int F, hipStream_t stream);
+extern "C" int fmda_gru_fwd_streams_launch(const void* gi, const void* w,
+                                           const float* bhh, void* out,
+                                           float* hlast, int S, int Tseq,
+                                           int n_dir, hipStream_t stream);
 extern "C" int fmda_pool_concat_launch(int is_bf16, const void* out,
                                        const float* hlast, void* feat, int B,
                                        int Tseq, int H, int Hp, int n_dir,
@@ -856,6 +864,90 @@ void ingest_row(torch::Tensor ring, torch::Tensor row, torch::Tensor xmin,
     TORCH_CHECK(rc == 0, "ingest_row launch failed rc=", rc);
 }
 
+// Batched ingest_row: rings (S, T, F) bf16, rows (S, F) fp32, active (S)
+// int32, xmin / xrng (S, F) fp32. Ring s is shifted and gets rows[s]
+// normalized with its own table iff active[s] != 0.
+void ingest_rows(torch::Tensor rings, torch::Tensor rows,
+                 torch::Tensor active, torch::Tensor xmin,
+                 torch::Tensor xrng) {
+    TORCH_CHECK(rings.is_cuda() && rings.is_contiguous() &&
+                rings.dim() == 3 &&
+                rings.scalar_type() == torch::kBFloat16,
+                "rings must be (S, T, F) bf16 on GPU");
+    const int64_t S = rings.size(0), T = rings.size(1), F = rings.size(2);
+    TORCH_CHECK(S >= 1 && T >= 1 && F >= 1 && S <= INT_MAX,
+                "ingest_rows: empty rings");
+    TORCH_CHECK((T - 1) * F <= 48 * 1024,
+                "ingest_rows: (T-1)*F = ", (T - 1) * F,
+                " exceeds the one-workgroup bound 49152");
+    TORCH_CHECK(rows.is_cuda() && rows.is_contiguous() &&
+                rows.scalar_type() == torch::kFloat32 && rows.dim() == 2 &&
+                rows.size(0) == S && rows.size(1) == F,
+                "rows must be fp32 (S, F) on GPU");
+    TORCH_CHECK(active.is_cuda() && active.is_contiguous() &&
+                active.scalar_type() == torch::kInt32 &&
+                active.dim() == 1 && active.size(0) == S,
+                "active must be int32 (S) on GPU");
+    TORCH_CHECK(xmin.is_cuda() && xmin.is_contiguous() &&
+                xmin.scalar_type() == torch::kFloat32 && xmin.dim() == 2 &&
+                xmin.size(0) == S && xmin.size(1) == F,
+                "xmin must be fp32 (S, F) on GPU");
+    TORCH_CHECK(xrng.is_cuda() && xrng.is_contiguous() &&
+                xrng.scalar_type() == torch::kFloat32 && xrng.dim() == 2 &&
+                xrng.size(0) == S && xrng.size(1) == F,
+                "xrng must be fp32 (S, F) on GPU");
+    TORCH_CHECK(rows.device() == rings.device() &&
+                active.device() == rings.device() &&
+                xmin.device() == rings.device() &&
+                xrng.device() == rings.device(),
+                "ingest_rows: tensors must share a device");
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_ingest_rows_launch(
+        rings.data_ptr(), rows.data_ptr<float>(), active.data_ptr<int>(),
+        xmin.data_ptr<float>(), xrng.data_ptr<float>(), (int)S, (int)T,
+        (int)F, stream.stream());
+    TORCH_CHECK(rc == 0, "ingest_rows launch failed rc=", rc);
+}
+
+// The batch-1 LDS-resident recurrence over S independent sequences: gi
+// (S, T, n_dir*3*128) bf16, w (n_dir, 384, 128) bf16, bhh (n_dir, 384) fp32
+// -> out (S, T, n_dir*128) bf16, h_last (n_dir, S, 128) fp32. Zero h0, no
+// dropout. Stream s gets the bits gru_fwd gives on gi[s:s+1].
+std::vector<torch::Tensor> gru_fwd_streams(torch::Tensor gi, torch::Tensor w,
+                                           torch::Tensor bhh) {
+    TORCH_CHECK(gi.is_cuda() && gi.is_contiguous() && gi.dim() == 3 &&
+                gi.scalar_type() == torch::kBFloat16,
+                "gru_fwd_streams: gi must be (S, T, n_dir*384) bf16 on GPU");
+    TORCH_CHECK(w.is_cuda() && w.is_contiguous() && w.dim() == 3 &&
+                w.scalar_type() == torch::kBFloat16 && w.size(2) == 128 &&
+                w.size(1) == 3 * 128 && (w.size(0) == 1 || w.size(0) == 2),
+                "gru_fwd_streams: w must be (n_dir, 384, 128) bf16 on GPU");
+    const int64_t n_dir = w.size(0), Hp = 128;
+    TORCH_CHECK(bhh.is_cuda() && bhh.is_contiguous() &&
+                bhh.scalar_type() == torch::kFloat32 &&
+                bhh.numel() == n_dir * 3 * Hp,
+                "gru_fwd_streams: bhh must be fp32 (n_dir, 384) on GPU");
+    TORCH_CHECK(w.device() == gi.device() && bhh.device() == gi.device(),
+                "gru_fwd_streams: tensors must share a device");
+    const int64_t S = gi.size(0), T = gi.size(1);
+    TORCH_CHECK(S >= 1 && S <= 65535 && T >= 1 && T <= INT_MAX,
+                "gru_fwd_streams: S must be in [1, 65535] and T >= 1");
+    TORCH_CHECK(gi.size(2) == n_dir * 3 * Hp,
+                "gru_fwd_streams: gi last dim must be n_dir*384");
+    auto out = torch::empty({S, T, n_dir * Hp}, gi.options());
+    auto hlast = torch::empty({n_dir, S, Hp},
+                              gi.options().dtype(torch::kFloat32));
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_gru_fwd_streams_launch(
+        gi.data_ptr(), w.data_ptr(), bhh.data_ptr<float>(), out.data_ptr(),
+        hlast.data_ptr<float>(), (int)S, (int)T, (int)n_dir,
+        stream.stream());
+    TORCH_CHECK(rc != -5, "gru_fwd_streams: T=", T,
+                " does not fit the 150 KB LDS cap");
+    TORCH_CHECK(rc == 0, "gru_fwd_streams launch failed rc=", rc);
+    return {out, hlast};
+}
+
 torch::Tensor pool_concat_infer(torch::Tensor out, torch::Tensor hlast,
                                 int64_t H) {
     TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 3);
@@ -1189,6 +1281,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "channel (Dropout2d) dropout over (B, T, F) without permutes");
     m.def("ingest_row", &ingest_row,
           "streaming ingest: shift GPU window ring + normalize new row");
+    m.def("ingest_rows", &ingest_rows,
+          "fleet ingest: ingest_row on the active rings of (S, T, F), each "
+          "with its own normalisation table",
+          py::arg("rings"), py::arg("rows"), py::arg("active"),
+          py::arg("xmin"), py::arg("xrng"));
+    m.def("gru_fwd_streams", &gru_fwd_streams,
+          "batch-1 LDS-resident recurrence over S independent sequences",
+          py::arg("gi"), py::arg("w"), py::arg("bhh"));
     m.def("pool_concat_infer", &pool_concat_infer,
           "fused [dirsum(h_last) | max | avg] concat for inference");
     m.def("head_sigmoid", &head_sigmoid,

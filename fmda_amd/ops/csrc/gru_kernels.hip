@@ -1214,15 +1214,18 @@ void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
 // MFMAs + one barrier per step per wave.
 // ===========================================================================
 
+// One block's work, shared by the single-sequence kernel and the
+// multi-stream kernel below: direction blockIdx.x of ONE sequence. gi and
+// out point at that sequence's slab, h0 (or null) at its (n_dir, Hp)
+// initial state; this direction's (Hp) fp32 h_last goes to hlast + hl_off.
 template <int Hp, int NT>
-__global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
-                          amdgpu_waves_per_eu(1, 1)))
-void gru_fwd_b1_kernel(const __hip_bfloat16* __restrict__ gi,
-                       const __hip_bfloat16* __restrict__ w,
-                       const float* __restrict__ bhh,
-                       __hip_bfloat16* __restrict__ out,
-                       float* __restrict__ hlast, int Tseq, int n_dir,
-                       const float* __restrict__ h0) {
+__device__ __forceinline__
+void gru_fwd_b1_body(const __hip_bfloat16* __restrict__ gi,
+                     const __hip_bfloat16* __restrict__ w,
+                     const float* __restrict__ bhh,
+                     __hip_bfloat16* __restrict__ out,
+                     float* __restrict__ hlast, int Tseq, int n_dir,
+                     const float* __restrict__ h0, long hl_off) {
     constexpr int NW = NT / 64;      // 4 waves
     constexpr int CT = Hp / 16;      // 8 h-column tiles
     constexpr int CPW = CT / NW;     // 2 per wave
@@ -1323,7 +1326,12 @@ void gru_fwd_b1_kernel(const __hip_bfloat16* __restrict__ gi,
                 const float r = sigmoidf((float)gt[j] + gr);
                 const float z = sigmoidf((float)gt[Hp + j] + gz);
                 const float n = fast_tanh((float)gt[2 * Hp + j] + r * hn);
-                const float hnew = (1.0f - z) * n + z * hreg[i];
+                // (1 - z) * n + z * h with the product z * h fused into the
+                // add. Spelled out because the contraction was the
+                // compiler's choice and did not survive this body being
+                // inlined into two kernels; this is the rounding the
+                // batch-1 kernel has always had.
+                const float hnew = __builtin_fmaf(z, hreg[i], (1.0f - z) * n);
                 hreg[i] = hnew;
                 const __bf16 hb = (__bf16)__float2bfloat16(hnew);
                 hw[j] = hb;
@@ -1337,11 +1345,46 @@ void gru_fwd_b1_kernel(const __hip_bfloat16* __restrict__ gi,
     }
 
     if ((lane >> 4) == 0) {
-        float* hl = hlast + (long)dir * Hp;   // (n_dir, B=1, Hp)
+        float* hl = hlast + hl_off;
 #pragma unroll
         for (int i = 0; i < CPW; ++i)
             hl[(wave + NW * i) * 16 + lane] = hreg[i];
     }
+}
+
+template <int Hp, int NT>
+__global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
+                          amdgpu_waves_per_eu(1, 1)))
+void gru_fwd_b1_kernel(const __hip_bfloat16* __restrict__ gi,
+                       const __hip_bfloat16* __restrict__ w,
+                       const float* __restrict__ bhh,
+                       __hip_bfloat16* __restrict__ out,
+                       float* __restrict__ hlast, int Tseq, int n_dir,
+                       const float* __restrict__ h0) {
+    gru_fwd_b1_body<Hp, NT>(gi, w, bhh, out, hlast, Tseq, n_dir, h0,
+                            (long)blockIdx.x * Hp);   // (n_dir, B=1, Hp)
+}
+
+// S independent sequences side by side (the fleet predict path): block
+// (d, s) is the batch-1 block for direction d on stream s's slab of
+// gi (S, T, n_dir*3Hp) and out (S, T, n_dir*Hp); hlast is (n_dir, S, Hp),
+// the layout pool_concat_infer reads for B = S. Zero h0. Blocks share
+// nothing, so up to one block per CU the S streams run in the latency of
+// one.
+template <int Hp, int NT>
+__global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
+                          amdgpu_waves_per_eu(1, 1)))
+void gru_fwd_streams_kernel(const __hip_bfloat16* __restrict__ gi,
+                            const __hip_bfloat16* __restrict__ w,
+                            const float* __restrict__ bhh,
+                            __hip_bfloat16* __restrict__ out,
+                            float* __restrict__ hlast, int Tseq, int n_dir) {
+    const long dir = blockIdx.x;
+    const long s = blockIdx.y;
+    const long S = gridDim.y;
+    gru_fwd_b1_body<Hp, NT>(
+        gi + s * Tseq * n_dir * 3 * Hp, w, bhh, out + s * Tseq * n_dir * Hp,
+        hlast, Tseq, n_dir, nullptr, (dir * S + s) * Hp);
 }
 
 // PHASES: diagnostic bitmask (1 = recompute GEMM, 2 = gate grads,
@@ -3271,6 +3314,47 @@ extern "C" int fmda_ingest_row_launch(void* ring, const float* row,
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// Batched ingest_row for the fleet path: block s shifts ring s of
+// rings (S, T, F) and appends rows[s] normalized with table s of
+// xmin / xrng (S, F) — the same expression as ingest_row_kernel — unless
+// active[s] == 0, in which case ring s is left untouched. The early return
+// is block-uniform and precedes the barrier.
+__global__ void ingest_rows_kernel(__hip_bfloat16* __restrict__ rings,
+                                   const float* __restrict__ rows,
+                                   const int* __restrict__ active,
+                                   const float* __restrict__ xmin,
+                                   const float* __restrict__ xrng,
+                                   int Tseq, int F) {
+    const long s = blockIdx.x;
+    if (active[s] == 0) return;
+    __hip_bfloat16* __restrict__ ring = rings + s * Tseq * F;
+    const float* __restrict__ row = rows + s * F;
+    const float* __restrict__ mn = xmin + s * F;
+    const float* __restrict__ rg = xrng + s * F;
+    const int n = (Tseq - 1) * F;
+    const int tid = threadIdx.x;
+    __hip_bfloat16 keep[48];
+    int cnt = 0;
+    for (int i = tid; i < n; i += blockDim.x) keep[cnt++] = ring[i + F];
+    __syncthreads();
+    cnt = 0;
+    for (int i = tid; i < n; i += blockDim.x) ring[i] = keep[cnt++];
+    for (int f = tid; f < F; f += blockDim.x)
+        ring[n + f] = __float2bfloat16((row[f] - mn[f]) / rg[f]);
+}
+
+extern "C" int fmda_ingest_rows_launch(void* rings, const float* rows,
+                                       const int* active, const float* xmin,
+                                       const float* xrng, int S, int Tseq,
+                                       int F, hipStream_t stream) {
+    const long n = ((long)Tseq - 1) * F;
+    if (n > 48 * 1024) return -5;   // window too large for one workgroup
+    if (S < 1) return -1;
+    ingest_rows_kernel<<<S, 1024, 0, stream>>>(
+        (__hip_bfloat16*)rings, rows, active, xmin, xrng, Tseq, F);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // Fused 3-way pooling head for inference: feat = concat[dirsum(h_last),
 // maxpool_T, avgpool_T] (biGRU_model.py:108-133) in ONE kernel — replaces
 // pool + hidden view/sum + cat (+ their launch latency) inside the
@@ -3816,6 +3900,26 @@ extern "C" int fmda_gru_fwd_b1_launch(const void* gi, const void* w,
     k<<<dim3(n_dir), 256, lds, stream>>>(
         (const __hip_bfloat16*)gi, (const __hip_bfloat16*)w, bhh,
         (__hip_bfloat16*)out, hlast, Tseq, n_dir, h0);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// S streams on a (n_dir, S) grid; same LDS requirement and cap as the
+// batch-1 launch. Above the cap nothing is launched.
+extern "C" int fmda_gru_fwd_streams_launch(const void* gi, const void* w,
+                                           const float* bhh, void* out,
+                                           float* hlast, int S, int Tseq,
+                                           int n_dir, hipStream_t stream) {
+    constexpr int Hp = 128;
+    const size_t lds = 2 * (size_t)Tseq * (3 * Hp + 8) + 2 * 2 * (Hp + 8) +
+                       4 * 3 * Hp;
+    if (lds > 150 * 1024) return -5;   // sequence too long for LDS residency
+    if (S < 1 || S > 65535) return -1;   // gridDim.y
+    auto k = gru_fwd_streams_kernel<Hp, 256>;
+    (void)hipFuncSetAttribute((const void*)k,
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    k<<<dim3(n_dir, S), 256, lds, stream>>>(
+        (const __hip_bfloat16*)gi, (const __hip_bfloat16*)w, bhh,
+        (__hip_bfloat16*)out, hlast, Tseq, n_dir);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

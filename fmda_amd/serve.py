@@ -15,6 +15,9 @@ HTTP instead of subscribing to a topic:
 Run: uvicorn "fmda_amd.serve:build_app_from_artifacts(...)" or see
 `create_app` for wiring an existing StreamingPredictor. On an MI355X the
 predictor's batch-1 step is the hipGraph-captured HIP engine path.
+
+`create_fleet_app` / `build_fleet_app_from_artifacts` are the same surface
+for a FleetPredictor: many symbols, one model, one captured tick.
 """
 import time
 from typing import Optional
@@ -28,6 +31,7 @@ try:
 except ImportError:  # pragma: no cover
     _PROM = False
 
+from .runtime.fleet import FleetPredictor
 from .runtime.streaming import StreamingPredictor
 
 
@@ -122,3 +126,122 @@ def build_app_from_artifacts(checkpoint: str = "model_params.pt",
     pred = StreamingPredictor(model, x_min, x_max, window, device=device,
                               dtype=dtype)
     return create_app(pred)
+
+
+def create_fleet_app(predictor: FleetPredictor):
+    """The multi-instrument surface: one model, S symbols, one tick.
+
+    - POST /ingest        {"rows": {symbol: [floats]}, "ts": optional}
+    - POST /timestamp     {"Timestamp": t}  -> score the whole fleet
+    - GET  /prediction/latest[?symbol=X]    -> last prediction per symbol
+    - GET  /healthz                         -> symbols, window, device,
+                                               per-symbol window_full
+    - GET  /metrics                         -> Prometheus exposition
+    """
+    from fastapi import FastAPI, HTTPException
+    from fastapi.responses import Response
+
+    app = FastAPI(title="fmda_amd fleet predictor")
+    latest = {}
+
+    if _PROM:
+        reg = CollectorRegistry()   # per app, as in create_app
+        c_pred = Counter("fmda_fleet_predictions_total",
+                         "predictions served", ["symbol"], registry=reg)
+        c_rows = Counter("fmda_fleet_rows_ingested_total",
+                         "feature rows pushed", ["symbol"], registry=reg)
+        c_stale = Counter("fmda_fleet_stale_dropped_total",
+                          "timestamp messages dropped as stale",
+                          registry=reg)
+        c_settle = Counter("fmda_fleet_settle_dropped_total",
+                           "symbols dropped from a tick because their row "
+                           "had not landed after the settle retry",
+                           registry=reg)
+        h_lat = Histogram(
+            "fmda_fleet_tick_latency_seconds", "fleet tick wall latency",
+            buckets=(1e-4, 2.5e-4, 5e-4, 1e-3, 2.5e-3, 5e-3, 1e-2, 5e-2),
+            registry=reg)
+
+    @app.post("/ingest")
+    def ingest(msg: dict):
+        rows = {s: torch.tensor(r, dtype=torch.float32)
+                for s, r in msg["rows"].items()}
+        try:
+            predictor.push_rows(rows, ts=msg.get("ts"))
+        except KeyError as e:
+            raise HTTPException(status_code=404, detail=str(e.args[0]))
+        if _PROM:
+            for s in rows:
+                c_rows.labels(symbol=s).inc()
+        return {"ok": True, "window_full": predictor.window_full()}
+
+    @app.post("/timestamp")
+    def timestamp(msg: dict):
+        t0 = time.perf_counter()
+        res = predictor.score_timestamp(msg)
+        if res["stale"]:
+            if _PROM:
+                c_stale.inc()
+            return {"ok": False, "reason": "stale"}
+        preds = res["predictions"]
+        latest.update(preds)
+        if _PROM:
+            c_settle.inc(len(res["dropped"]))
+            for s in preds:
+                c_pred.labels(symbol=s).inc()
+            if preds:
+                h_lat.observe(time.perf_counter() - t0)
+        return {"ok": bool(preds), "predictions": preds,
+                "dropped": res["dropped"], "not_full": res["not_full"]}
+
+    @app.get("/prediction/latest")
+    def latest_prediction(symbol: Optional[str] = None):
+        if symbol is None:
+            return {"predictions": dict(latest)}
+        if symbol not in predictor.symbols:
+            raise HTTPException(status_code=404,
+                                detail=f"unknown symbol {symbol!r}")
+        return {"prediction": latest.get(symbol)}
+
+    @app.get("/healthz")
+    def healthz():
+        return {"ok": True,
+                "symbols": list(predictor.symbols),
+                "device": str(predictor.device),
+                "window": predictor.window,
+                "n_features": predictor.n_features,
+                "route": predictor.route,
+                "window_full": predictor.window_full(),
+                "n_predictions": predictor.n_predictions}
+
+    @app.get("/metrics")
+    def metrics():
+        if not _PROM:  # pragma: no cover
+            return Response("prometheus_client not installed",
+                            media_type="text/plain")
+        return Response(generate_latest(reg),
+                        media_type=CONTENT_TYPE_LATEST)
+
+    return app
+
+
+def build_fleet_app_from_artifacts(checkpoint: str = "model_params.pt",
+                                   norm_params: str = "norm_params",
+                                   symbols=(),
+                                   window: int = 30,
+                                   device: Optional[str] = None):
+    """Fleet app factory from the reference-format artifacts; the one
+    norm_params table is applied to every symbol."""
+    from .data.norm import load_norm_params
+    from .models.checkpoint import load_checkpoint
+
+    model = load_checkpoint(checkpoint)
+    _, x_min, x_max = load_norm_params(norm_params)
+    if device is None:
+        device = "cuda:0" if torch.cuda.is_available() else "cpu"
+    dtype = torch.bfloat16 if device.startswith("cuda") else torch.float32
+    if dtype is torch.bfloat16:
+        model = model.to(dtype)
+    pred = FleetPredictor(model, list(symbols), x_min, x_max, window,
+                          device=device, dtype=dtype)
+    return create_fleet_app(pred)
