@@ -1387,6 +1387,85 @@ void gru_fwd_streams_kernel(const __hip_bfloat16* __restrict__ gi,
         hlast, Tseq, n_dir, nullptr, (dir * S + s) * Hp);
 }
 
+// Exact exchanges inside aligned groups of 8 lanes: lane l receives the
+// operand of lane l ^ 4 (ds_swizzle, bit-mask mode: and 0x1F, or 0, xor 4),
+// l ^ 2 (DPP quad_perm [2,3,0,1]) or l ^ 1 (DPP quad_perm [1,0,3,2]). All
+// lanes of the wave must be active.
+FMDA_DEV unsigned int lane_xor4(unsigned int v) {
+    return (unsigned int)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);
+}
+FMDA_DEV unsigned int lane_xor2(unsigned int v) {
+    return (unsigned int)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);
+}
+FMDA_DEV unsigned int lane_xor1(unsigned int v) {
+    return (unsigned int)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
+}
+
+// 8 x 8 byte transpose across an aligned group of 8 lanes: lane k (= lane
+// & 7) passes the 8 bytes of x_k; on return byte c of lane l's value is byte
+// l of x_c. Three butterfly stages, each swapping one lane bit with one
+// byte-index bit (dword, 16-bit half, byte): one cross-lane move per stage.
+FMDA_DEV unsigned long long transpose_bytes8(unsigned long long x, int lane) {
+    unsigned int lo = (unsigned int)x, hi = (unsigned int)(x >> 32);
+    const bool l2 = (lane & 4) != 0, l1 = (lane & 2) != 0,
+               l0 = (lane & 1) != 0;
+    unsigned int r = lane_xor4(l2 ? lo : hi);
+    if (l2) lo = r; else hi = r;
+    r = lane_xor2(l1 ? ((lo & 0xFFFFu) | (hi << 16))
+                     : ((lo >> 16) | (hi & 0xFFFF0000u)));
+    if (l1) {
+        lo = (lo & 0xFFFF0000u) | (r & 0xFFFFu);
+        hi = (hi & 0xFFFF0000u) | (r >> 16);
+    } else {
+        lo = (lo & 0xFFFFu) | (r << 16);
+        hi = (hi & 0xFFFFu) | (r & 0xFFFF0000u);
+    }
+    // v_perm_b32 selectors: bytes 0..3 index the second operand, 4..7 the
+    // first. Odd lanes hand over their even bytes, even lanes their odd ones.
+    r = lane_xor1(__builtin_amdgcn_perm(hi, lo,
+                                        l0 ? 0x06040200u : 0x07050301u));
+    const unsigned int nlo =
+        __builtin_amdgcn_perm(r, lo, l0 ? 0x03050104u : 0x05020400u);
+    const unsigned int nhi =
+        __builtin_amdgcn_perm(r, hi, l0 ? 0x03070106u : 0x07020600u);
+    return ((unsigned long long)nhi << 32) | nlo;
+}
+
+// store_tile with the per-thread addressing formed by the caller, once: chunk
+// n of the thread sits at LDS byte `n * NT * 16 + (PAD ? r16[n] : 0)` past
+// `lds` (which already includes tid * 16) and goes to `gp + goff[n]`; its row
+// is live when r16[n] < rv16 (= rows_valid * 16). A full block issues the
+// tile's LDS reads together and then its stores, with no predicate; the
+// tail block predicates each chunk as store_tile does. `__restrict__` as in
+// store_tile: the tile read here is never a target of an LDS DMA in flight.
+template <int SPT, int NT, bool PAD>
+FMDA_DEV void store_tile_pre(const char* __restrict__ lds,
+                             char* __restrict__ gp,
+                             const unsigned int (&goff)[SPT],
+                             const unsigned int (&r16)[SPT],
+                             unsigned int rv16, bool full) {
+    if (full) {
+        typedef unsigned int st_u32x4 __attribute__((ext_vector_type(4)));
+        static_assert(SPT == 3, "the pin below names three chunks");
+        st_u32x4 v[SPT];
+#pragma unroll
+        for (int n = 0; n < SPT; ++n)
+            v[n] = *(const st_u32x4*)(lds + n * NT * 16 +
+                                      (PAD ? r16[n] : 0u));
+        // pin all three reads ahead of the first store (the empty asm needs
+        // every value): one LDS round trip per tile instead of one per chunk
+        asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]));
+#pragma unroll
+        for (int n = 0; n < SPT; ++n) *(st_u32x4*)(gp + goff[n]) = v[n];
+    } else {
+#pragma unroll
+        for (int n = 0; n < SPT; ++n)
+            if (r16[n] < rv16)
+                *(chunk16*)(gp + goff[n]) = *(const chunk16*)(
+                    lds + n * NT * 16 + (PAD ? r16[n] : 0u));
+    }
+}
+
 // PHASES: diagnostic bitmask (1 = recompute GEMM, 2 = gate grads,
 // 4 = carry GEMM). Production uses 7; other masks exist only so
 // scripts/kernel_micro.py can time each phase's contribution to the
@@ -1678,6 +1757,52 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
                                        ksw * 16 + within);
     };
 
+    // Fused-dropout mask, one draw per octet: the element at (b, tt, dir, j)
+    // takes byte o & 7 of mix64(seed ^ (o >> 3)), o = ((b0 + b) * Tseq + tt)
+    // * n_dir * Hp + dir * Hp + j. In the MFMA C layout j = ct * 16 +
+    // (lane & 15) and n_dir * Hp, dir * Hp are multiples of 8, so o & 7 =
+    // lane & 7 and, for each of the thread's 8 elements of a step, the 8
+    // lanes of an aligned group share one octet. Lane k of the group hashes
+    // the octet of element k = (i * MT + m) * 4 + e (the order phase B
+    // visits them) and transpose_bytes8 hands every lane its byte of all 8
+    // draws. oct0 is that octet at tt = 0; a step adds tt * n_dir * (Hp / 8).
+    static_assert(Hp % 16 == 0, "octets must not straddle column tiles");
+    static_assert(POOLED || CPW * MT * 4 == 8,
+                  "the dropout exchange covers 8 elements per thread");
+    const bool dropping = !POOLED && drop_thr != 0u;
+    long oct0 = 0;
+    if (dropping) {
+        const int k = lane & 7;
+        const int ik = k / (4 * MT), mk = (k >> 2) % MT, ek = k & 3;
+        const int bk = 16 * mk + 4 * (lane >> 4) + ek;
+        const int jk = (wave + NW * ik) * 16 + (lane & 15);
+        oct0 = ((long)(b0 + bk) * Tseq * n_dir * Hp + (long)dir * Hp + jk) >> 3;
+    }
+    const long oct_step = (long)n_dir * (Hp / 8);
+
+    // Step-invariant addressing of the one-step-late dGi / dGh tile stores:
+    // chunk c = tid + n * NT of a tile sits in row r = c / CPR at chunk
+    // c % CPR, for both tiles (same global layout). Its byte offset from
+    // the tile's (uniform) time-step base and r * 16 (the dgh_s pad; also
+    // the rows_valid predicate) are formed once here; the gi tile's LDS
+    // offset is c * 16, the padded dgh tile's c * 16 + r * 16. 32-bit
+    // offsets when a block's BT rows span less than 2 GiB, else store_tile.
+    constexpr int SPT = NST / 2;                 // chunks per thread and tile
+    constexpr int CPR = (GP * 2) / 16;           // 16-byte chunks per row
+    static_assert(SPT * NT == BT * CPR && GP3 * 2 == CPR * 16 + 16,
+                  "store addressing mismatch");
+    const bool st_fast = (long)BT * gi_row * 2 < (1L << 31);
+    unsigned int st_goff[SPT], st_r16[SPT];
+#pragma unroll
+    for (int n = 0; n < SPT; ++n) {
+        const int c = tid + n * NT;
+        const int r = c / CPR;
+        st_goff[n] = (unsigned int)r * (unsigned int)(gi_row * 2) +
+                     (unsigned int)(c % CPR) * 16u;
+        st_r16[n] = (unsigned int)r * 16u;
+    }
+    const unsigned int rv16 = (unsigned int)rows_valid * 16u;
+
     {   // prologue: stage step Tseq-1 inputs
         const int u = Tseq - 1;
         const int tt = rev ? 0 : u;
@@ -1717,14 +1842,34 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
             // needed (the single per-step barrier is at B-end, where it
             // also rendezvouses this step's DMA).
             const int ttp = rev ? (Tseq - 2 - u) : (u + 1);
-            store_tile<__hip_bfloat16, BT, NT>(
-                gi_slot((u + 1) % 3), dgi_b + (long)ttp * n_dir * 3 * Hp, GP, GP,
-                gi_row, rows_valid, tid);
             const int sh = rev ? (ttp + 1) : (ttp - 1);  // always in range
-            store_tile<__hip_bfloat16, BT, NT>(
-                dgh_buf(1 - q), dgh_b + (long)sh * n_dir * 3 * Hp, GP, GP3,
-                gi_row, rows_valid, tid);
+            if (st_fast) {
+                // only the two uniform bases depend on the step
+                store_tile_pre<SPT, NT, false>(
+                    (const char*)gi_slot((u + 1) % 3) + tid * 16,
+                    (char*)(dgi_b + (long)ttp * n_dir * 3 * Hp), st_goff,
+                    st_r16, rv16, rows_valid == BT);
+                store_tile_pre<SPT, NT, true>(
+                    (const char*)dgh_buf(1 - q) + tid * 16,
+                    (char*)(dgh_b + (long)sh * n_dir * 3 * Hp), st_goff,
+                    st_r16, rv16, rows_valid == BT);
+            } else {
+                store_tile<__hip_bfloat16, BT, NT>(
+                    gi_slot((u + 1) % 3), dgi_b + (long)ttp * n_dir * 3 * Hp,
+                    GP, GP, gi_row, rows_valid, tid);
+                store_tile<__hip_bfloat16, BT, NT>(
+                    dgh_buf(1 - q), dgh_b + (long)sh * n_dir * 3 * Hp, GP,
+                    GP3, gi_row, rows_valid, tid);
+            }
         }
+
+        // this step's 8 mask bytes (byte k: element k), off the gate chain
+        unsigned long long dmask = 0ull;
+        if (dropping)
+            dmask = transpose_bytes8(
+                mix64(drop_seed ^
+                      (unsigned long long)(oct0 + (long)tt * oct_step)),
+                lane);
 
         // ---- phase B: recompute GEMM, then fused gate gradients ----
         const __hip_bfloat16* hbq = hb_buf(q);
@@ -1801,14 +1946,12 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
                         // grad w.r.t. the DROPPED activations; recompute
                         // the counter-based mask (same splitmix64 draw as
                         // dropout_kernel) instead of a separate 1 GB
-                        // read+write pass over d_out.
-                        const long o = ((long)(b0 + b) * Tseq + tt) *
-                                           n_dir * Hp +
-                                       (long)dir * Hp + j;
-                        const unsigned long long rnd =
-                            mix64(drop_seed ^ (unsigned long long)(o >> 3));
+                        // read+write pass over d_out. dmask holds this
+                        // element's byte of its octet's draw (see oct0).
                         const unsigned int u =
-                            (unsigned int)(rnd >> (8 * ((int)o & 7))) & 0xFF;
+                            (unsigned int)(dmask >>
+                                           (8 * ((i * MT + m) * 4 + e))) &
+                            0xFF;
                         doval = (u < drop_thr) ? 0.0f : doval * drop_scale;
                     }
                     const float dht = dhreg[i][m][e] + doval;
@@ -1851,6 +1994,11 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
         // operations of every thread of a full block, vmcnt(NST) still
         // means "every DMA of this step has landed", and the tail block
         // still drains to zero.
+        // store_tile_pre issues the same NST stores as the two store_tile
+        // calls it stands in for (unpredicated in a full block, SPT per
+        // tile), after the DMAs and with LDS reads only in between; the
+        // dropout mask's hash and lane exchange (DPP, ds_swizzle: lgkmcnt)
+        // add no vector-memory operation. The quota and the order hold.
         if (have_next) {
             if (have_prev && rows_valid == BT)
                 asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NST) : "memory");

@@ -22,6 +22,11 @@ def main():
     ap.add_argument("--H", type=int, default=128)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--what", default="both", help="fwd|bwd|both")
+    ap.add_argument("--drop-p", type=float, default=0.0,
+                    help="fused inter-layer dropout of the backward "
+                         "(gru_bwd's drop_p; 0 = none, as for a top layer)")
+    ap.add_argument("--seed", type=int, default=0,
+                    help="dropout seed passed to gru_bwd")
     args = ap.parse_args()
     ext = load_extension()
     B, T, Hp = args.B, args.T, args.H
@@ -38,7 +43,7 @@ def main():
         return ext.gru_fwd(gi, w, bhh)
 
     def run_bwd():
-        return ext.gru_bwd(gi, w, bhh, out, dout, dhT)
+        return ext.gru_bwd(gi, w, bhh, out, dout, dhT, args.drop_p, args.seed)
 
     cases = [("fwd", run_fwd), ("bwd", run_bwd)]
 
@@ -70,8 +75,9 @@ def main():
         torch.cuda.synchronize()
         us = (time.perf_counter() - t0) / args.iters * 1e6
         per_step = us / T * 1000.0
+        extra = f" drop_p={args.drop_p}" if name == "bwd" else ""
         print(f"{name}: {us:9.1f} us  ({per_step:6.1f} ns/step, "
-              f"B={B} T={T} Hp={Hp})", flush=True)
+              f"B={B} T={T} Hp={Hp}{extra})", flush=True)
 
 
 if __name__ == "__main__":
