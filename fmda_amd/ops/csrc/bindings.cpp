@@ -93,6 +93,18 @@ extern "C" int fmda_gru_fwd_streams_launch(const void* gi, const void* w,
                                            const float* bhh, void* out,
                                            float* hlast, int S, int Tseq,
                                            int n_dir, hipStream_t stream);
+extern "C" int fmda_gru_fwd_streams_bank_launch(
+    const void* gi, const int* slot, int M, const void* w, const float* bhh,
+    void* out, float* hlast, int S, int Tseq, int n_dir, hipStream_t stream);
+extern "C" int fmda_gi_proj_bank_launch(const void* x, const int* slot,
+                                        const void* W, const void* b,
+                                        void* gi, int S, int Tseq, int K,
+                                        int N, int M, hipStream_t stream);
+extern "C" int fmda_head_sigmoid_bank_launch(const void* x, const int* slot,
+                                             const void* W, const void* bias,
+                                             float* probs, int B, int K,
+                                             int C, int M,
+                                             hipStream_t stream);
 extern "C" int fmda_pool_concat_launch(int is_bf16, const void* out,
                                        const float* hlast, void* feat, int B,
                                        int Tseq, int H, int Hp, int n_dir,
@@ -985,6 +997,139 @@ torch::Tensor head_sigmoid(torch::Tensor x, torch::Tensor W,
     return probs;
 }
 
+// ---- a bank of M models behind a per-stream slot index ----
+// The three ops below read slot (int32 (S), on the device) inside the
+// kernel, make no host sync and launch on the current stream, so a captured
+// graph follows the index between replays. The kernels clamp what they read
+// into [0, M); rejecting a bad index is the caller's job, before the write.
+
+namespace {
+
+void check_bank_slot(const torch::Tensor& slot, const torch::Tensor& like,
+                     int64_t S, const char* op) {
+    TORCH_CHECK(slot.is_cuda() && slot.is_contiguous() &&
+                slot.scalar_type() == torch::kInt32 && slot.dim() == 1 &&
+                slot.size(0) == S,
+                op, ": slot must be int32 (S) on GPU");
+    TORCH_CHECK(slot.device() == like.device(),
+                op, ": tensors must share a device");
+    TORCH_CHECK(S >= 1 && S <= 65535, op, ": S must be in [1, 65535]");
+}
+
+bool bf16_cuda(const torch::Tensor& t, int64_t rank) {
+    return t.is_cuda() && t.is_contiguous() && t.dim() == rank &&
+           t.scalar_type() == torch::kBFloat16;
+}
+
+}  // namespace
+
+// gi[s] = x[s] @ W[slot[s]]^T + b[slot[s]]: x (S, T, K), W (M, N, K),
+// b (M, N) -> gi (S, T, N), bf16 with fp32 accumulation.
+torch::Tensor gi_proj_bank(torch::Tensor x, torch::Tensor slot,
+                           torch::Tensor W, torch::Tensor b) {
+    TORCH_CHECK(bf16_cuda(x, 3),
+                "gi_proj_bank: x must be (S, T, K) bf16 on GPU");
+    TORCH_CHECK(bf16_cuda(W, 3),
+                "gi_proj_bank: W must be (M, N, K) bf16 on GPU");
+    TORCH_CHECK(bf16_cuda(b, 2),
+                "gi_proj_bank: b must be (M, N) bf16 on GPU");
+    const int64_t S = x.size(0), T = x.size(1), K = x.size(2);
+    const int64_t M = W.size(0), N = W.size(1);
+    check_bank_slot(slot, x, S, "gi_proj_bank");
+    TORCH_CHECK(W.device() == x.device() && b.device() == x.device(),
+                "gi_proj_bank: tensors must share a device");
+    TORCH_CHECK(M >= 1 && W.size(2) == K && b.size(0) == M && b.size(1) == N,
+                "gi_proj_bank: W (M, N, K) and b (M, N) must agree with x's "
+                "K and with each other, M >= 1");
+    TORCH_CHECK(N >= 16 && N % 16 == 0 && N <= INT_MAX,
+                "gi_proj_bank: N must be a multiple of 16");
+    TORCH_CHECK(T >= 1 && T <= 65535 * 32 && K >= 1 && K <= INT_MAX &&
+                M <= INT_MAX && M * N <= INT_MAX,
+                "gi_proj_bank: T must be in [1, 65535*32] and K >= 1");
+    auto gi = torch::empty({S, T, N}, x.options());
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_gi_proj_bank_launch(
+        x.data_ptr(), slot.data_ptr<int>(), W.data_ptr(), b.data_ptr(),
+        gi.data_ptr(), (int)S, (int)T, (int)K, (int)N, (int)M,
+        stream.stream());
+    TORCH_CHECK(rc == 0, "gi_proj_bank launch failed rc=", rc);
+    return gi;
+}
+
+// gru_fwd_streams with stream s on the recurrent weights of slot[s]:
+// w (M, n_dir, 384, 128) bf16, bhh (M, n_dir, 384) fp32. Stream s gets the
+// bits gru_fwd_streams gives on gi[s:s+1] with w[slot[s]], bhh[slot[s]].
+std::vector<torch::Tensor> gru_fwd_streams_bank(torch::Tensor gi,
+                                                torch::Tensor slot,
+                                                torch::Tensor w,
+                                                torch::Tensor bhh) {
+    TORCH_CHECK(bf16_cuda(gi, 3),
+                "gru_fwd_streams_bank: gi must be (S, T, n_dir*384) bf16 on "
+                "GPU");
+    TORCH_CHECK(bf16_cuda(w, 4) && w.size(0) >= 1 && w.size(3) == 128 &&
+                w.size(2) == 3 * 128 && (w.size(1) == 1 || w.size(1) == 2),
+                "gru_fwd_streams_bank: w must be (M, n_dir, 384, 128) bf16 "
+                "on GPU, M >= 1");
+    const int64_t M = w.size(0), n_dir = w.size(1), Hp = 128;
+    TORCH_CHECK(bhh.is_cuda() && bhh.is_contiguous() &&
+                bhh.scalar_type() == torch::kFloat32 && bhh.dim() == 3 &&
+                bhh.size(0) == M && bhh.size(1) == n_dir &&
+                bhh.size(2) == 3 * Hp,
+                "gru_fwd_streams_bank: bhh must be fp32 (M, n_dir, 384) on "
+                "GPU");
+    const int64_t S = gi.size(0), T = gi.size(1);
+    check_bank_slot(slot, gi, S, "gru_fwd_streams_bank");
+    TORCH_CHECK(w.device() == gi.device() && bhh.device() == gi.device(),
+                "gru_fwd_streams_bank: tensors must share a device");
+    TORCH_CHECK(T >= 1 && T <= INT_MAX && M <= INT_MAX,
+                "gru_fwd_streams_bank: T must be >= 1");
+    TORCH_CHECK(gi.size(2) == n_dir * 3 * Hp,
+                "gru_fwd_streams_bank: gi last dim must be n_dir*384");
+    auto out = torch::empty({S, T, n_dir * Hp}, gi.options());
+    auto hlast = torch::empty({n_dir, S, Hp},
+                              gi.options().dtype(torch::kFloat32));
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_gru_fwd_streams_bank_launch(
+        gi.data_ptr(), slot.data_ptr<int>(), (int)M, w.data_ptr(),
+        bhh.data_ptr<float>(), out.data_ptr(), hlast.data_ptr<float>(),
+        (int)S, (int)T, (int)n_dir, stream.stream());
+    TORCH_CHECK(rc != -5, "gru_fwd_streams_bank: T=", T,
+                " does not fit the 150 KB LDS cap");
+    TORCH_CHECK(rc == 0, "gru_fwd_streams_bank launch failed rc=", rc);
+    return {out, hlast};
+}
+
+// head_sigmoid with row s on the head of slot[s]: feat (S, K), W (M, C, K),
+// b (M, C) bf16 -> probs (S, C) fp32.
+torch::Tensor head_sigmoid_bank(torch::Tensor feat, torch::Tensor slot,
+                                torch::Tensor W, torch::Tensor b) {
+    TORCH_CHECK(bf16_cuda(feat, 2),
+                "head_sigmoid_bank: feat must be (S, K) bf16 on GPU");
+    TORCH_CHECK(bf16_cuda(W, 3),
+                "head_sigmoid_bank: W must be (M, C, K) bf16 on GPU");
+    TORCH_CHECK(bf16_cuda(b, 2),
+                "head_sigmoid_bank: b must be (M, C) bf16 on GPU");
+    const int64_t S = feat.size(0), K = feat.size(1);
+    const int64_t M = W.size(0), C = W.size(1);
+    check_bank_slot(slot, feat, S, "head_sigmoid_bank");
+    TORCH_CHECK(W.device() == feat.device() && b.device() == feat.device(),
+                "head_sigmoid_bank: tensors must share a device");
+    TORCH_CHECK(M >= 1 && C >= 1 && K >= 1 && W.size(2) == K &&
+                b.size(0) == M && b.size(1) == C,
+                "head_sigmoid_bank: W (M, C, K) and b (M, C) must agree "
+                "with feat's K and with each other, M >= 1");
+    TORCH_CHECK(K <= INT_MAX && S * C <= INT_MAX && M * C <= INT_MAX,
+                "head_sigmoid_bank: sizes exceed int range");
+    auto probs = torch::empty({S, C}, feat.options().dtype(torch::kFloat32));
+    auto stream = at::hip::getCurrentHIPStream();
+    int rc = fmda_head_sigmoid_bank_launch(
+        feat.data_ptr(), slot.data_ptr<int>(), W.data_ptr(), b.data_ptr(),
+        probs.data_ptr<float>(), (int)S, (int)K, (int)C, (int)M,
+        stream.stream());
+    TORCH_CHECK(rc == 0, "head_sigmoid_bank launch failed rc=", rc);
+    return probs;
+}
+
 namespace {
 
 void check_f32_cuda(const torch::Tensor& t, const char* what) {
@@ -1289,6 +1434,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gru_fwd_streams", &gru_fwd_streams,
           "batch-1 LDS-resident recurrence over S independent sequences",
           py::arg("gi"), py::arg("w"), py::arg("bhh"));
+    m.def("gi_proj_bank", &gi_proj_bank,
+          "grouped input projection: stream s through W[slot[s]], b[slot[s]]",
+          py::arg("x"), py::arg("slot"), py::arg("W"), py::arg("b"));
+    m.def("gru_fwd_streams_bank", &gru_fwd_streams_bank,
+          "gru_fwd_streams with stream s on the recurrent weights of slot[s]",
+          py::arg("gi"), py::arg("slot"), py::arg("w"), py::arg("bhh"));
+    m.def("head_sigmoid_bank", &head_sigmoid_bank,
+          "head_sigmoid with row s on the head of slot[s]",
+          py::arg("feat"), py::arg("slot"), py::arg("W"), py::arg("b"));
     m.def("pool_concat_infer", &pool_concat_infer,
           "fused [dirsum(h_last) | max | avg] concat for inference");
     m.def("head_sigmoid", &head_sigmoid,

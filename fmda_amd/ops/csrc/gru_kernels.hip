@@ -43,6 +43,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <cstdint>
+
 #include "dropout_common.h"   // mix64, drop_hit, drop_apply
 
 #define FMDA_DEV __device__ __forceinline__
@@ -1385,6 +1387,192 @@ void gru_fwd_streams_kernel(const __hip_bfloat16* __restrict__ gi,
     gru_fwd_b1_body<Hp, NT>(
         gi + s * Tseq * n_dir * 3 * Hp, w, bhh, out + s * Tseq * n_dir * Hp,
         hlast, Tseq, n_dir, nullptr, (dir * S + s) * Hp);
+}
+
+// A per-stream slot index into a bank of M models, read on the device so a
+// captured graph follows it between replays. Clamped into [0, M): a bad
+// index reads another model's weights, never memory outside the bank (the
+// host rejects bad indices before it writes them).
+FMDA_DEV long bank_slot(const int* __restrict__ slot, long s, int M) {
+    const int m = slot[s];
+    return m < 0 ? 0 : (m >= M ? M - 1 : m);
+}
+
+// gru_fwd_streams over a bank of models: w is (M, n_dir, 3Hp, Hp), bhh
+// (M, n_dir, 3Hp), and block (d, s) runs the unchanged batch-1 body on the
+// W_hh / b_hh of slot[s]. Same grid, LDS and output layouts as
+// gru_fwd_streams_kernel; the body loads its own fragments per block, so
+// the bank costs one index load.
+template <int Hp, int NT>
+__global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
+                          amdgpu_waves_per_eu(1, 1)))
+void gru_fwd_streams_bank_kernel(const __hip_bfloat16* __restrict__ gi,
+                                 const int* __restrict__ slot, int M,
+                                 const __hip_bfloat16* __restrict__ w,
+                                 const float* __restrict__ bhh,
+                                 __hip_bfloat16* __restrict__ out,
+                                 float* __restrict__ hlast, int Tseq,
+                                 int n_dir) {
+    const long dir = blockIdx.x;
+    const long s = blockIdx.y;
+    const long S = gridDim.y;
+    const long m = bank_slot(slot, s, M);
+    gru_fwd_b1_body<Hp, NT>(
+        gi + s * Tseq * n_dir * 3 * Hp, w + m * n_dir * 3 * Hp * Hp,
+        bhh + m * n_dir * 3 * Hp, out + s * Tseq * n_dir * Hp,
+        hlast, Tseq, n_dir, nullptr, (dir * S + s) * Hp);
+}
+
+// ---------------------------------------------------------------------------
+// Grouped input projection over a bank of models:
+//   gi[s] = x[s] @ W[slot[s]]^T + b[slot[s]]
+// x (S, T, K), W (M, N, K), b (M, N), gi (S, T, N), all bf16. One launch
+// covers every stream; the library GEMM it replaces takes one W.
+//
+// Both operands are K-contiguous, which is the per-lane order of the MFMA
+// A and B fragments (8 consecutive k per lane), so fragments load straight
+// from global memory and the kernel uses no LDS. W is the A operand and x
+// the B operand: the accumulator then holds gi^T, lane l owning 4
+// consecutive n of ONE time row, which it rounds once and writes with one
+// 8-byte store. A wave owns a 64-column x 32-row tile of one stream's gi:
+// per k-step four W fragments and two x fragments feed eight MFMAs, and
+// two k-steps of loads are in flight before their MFMAs (a 16 x 32 tile
+// with one step in flight measured 24.9 us per launch at S = 64, T = 120,
+// bound by fragment traffic: profiles/fleet_bank.md). Grid (ceil(N/256),
+// S, row tiles), 4 waves per block. Every output element is the same
+// K/32-step MFMA chain whatever its stream, slot or tile, so streams are
+// independent bit for bit.
+//
+// VEC is the widest load the row pitch 2*K bytes keeps aligned: 8 elements
+// (16 bytes) when K % 8 == 0, 4 when K % 4 == 0 (K = 108: rows are only
+// 8-byte aligned), else single elements. Elements at k >= K and rows at
+// t >= T are zero in the fragment and are not read.
+// ---------------------------------------------------------------------------
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+
+template <int VEC>
+FMDA_DEV bf16x8_t load_krow_frag(const __bf16* __restrict__ row, int k0,
+                                 int K) {
+    bf16x8_t f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = (__bf16)0.0f;
+    if constexpr (VEC == 8) {
+        if (k0 < K) f = *(const bf16x8_t*)(row + k0);
+    } else if constexpr (VEC == 4) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (k0 + 4 * h < K) {
+                const bf16x4_t v = *(const bf16x4_t*)(row + k0 + 4 * h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) f[4 * h + e] = v[e];
+            }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (k0 + e < K) f[e] = row[k0 + e];
+    }
+    return f;
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256)
+void gi_proj_bank_kernel(const __hip_bfloat16* __restrict__ x,
+                         const int* __restrict__ slot,
+                         const __hip_bfloat16* __restrict__ W,
+                         const __hip_bfloat16* __restrict__ b,
+                         __hip_bfloat16* __restrict__ gi, int Tseq, int K,
+                         int N, int M) {
+    constexpr int KU = 2;        // k-steps of loads in flight
+    constexpr int NTW = 4;       // 16-column tiles of N per wave
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int nw = (blockIdx.x * 4 + wave) * NTW * 16;   // first column
+    if (nw >= N) return;                         // no barriers below
+    const long s = blockIdx.y;
+    const long m = bank_slot(slot, s, M);
+    const int r16 = lane & 15;
+    const int kl = 8 * (lane >> 4);
+    const int q4 = 4 * (lane >> 4);              // this lane's 4 columns
+
+    const __bf16* xs = (const __bf16*)x + s * Tseq * K;
+    // N is a multiple of 16, not of 64: a tile past N loads and stores
+    // nothing (Kw = 0 zero-fills its fragments); wave-uniform
+    const __bf16* wrow[NTW];
+    int Kw[NTW];
+    float bias[NTW][4];
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) {
+        const int nt = nw + 16 * i;
+        const bool ok = nt < N;
+        Kw[i] = ok ? K : 0;
+        wrow[i] = (const __bf16*)W + (m * N + (ok ? nt + r16 : 0)) * K;
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            bias[i][v] = ok ? (float)((const __bf16*)b)[m * N + (ok ? nt : 0)
+                                                        + q4 + v]
+                            : 0.0f;
+    }
+
+    {
+        const int t0 = blockIdx.z * 32;          // < Tseq by the grid
+        const bool two = t0 + 16 < Tseq;         // wave-uniform
+        const int ta = t0 + r16, tb = ta + 16;
+        const int Ka = ta < Tseq ? K : 0, Kb = tb < Tseq ? K : 0;
+        const __bf16* xa = xs + (long)(ta < Tseq ? ta : Tseq - 1) * K;
+        const __bf16* xb = xs + (long)(tb < Tseq ? tb : Tseq - 1) * K;
+        f32x4_t acc[NTW][2];
+#pragma unroll
+        for (int i = 0; i < NTW; ++i)
+            acc[i][0] = acc[i][1] = f32x4_t{0.f};
+        // KU k-steps of loads in flight before their MFMAs
+        for (int kb = 0; kb < K; kb += 32 * KU) {
+            bf16x8_t wf[KU][NTW], fa[KU], fb[KU];
+#pragma unroll
+            for (int j = 0; j < KU; ++j) {
+                const int k0 = kb + 32 * j + kl;
+#pragma unroll
+                for (int i = 0; i < NTW; ++i)
+                    wf[j][i] = load_krow_frag<VEC>(wrow[i], k0, Kw[i]);
+                fa[j] = load_krow_frag<VEC>(xa, k0, Ka);
+                fb[j] = load_krow_frag<VEC>(xb, k0, Kb);
+            }
+#pragma unroll
+            for (int j = 0; j < KU; ++j) {
+                if (kb + 32 * j >= K) break;     // wave-uniform
+#pragma unroll
+                for (int i = 0; i < NTW; ++i) {
+                    acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        wf[j][i], fa[j], acc[i][0], 0, 0, 0);
+                    if (two)
+                        acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            wf[j][i], fb[j], acc[i][1], 0, 0, 0);
+                }
+            }
+        }
+        // C[row = n][col = t]: lane l holds 4 consecutive n of time row
+        // t0 + l%16 (and of t0 + 16 + l%16)
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) {
+            if (nw + 16 * i >= N) break;         // wave-uniform
+            __bf16* gs = (__bf16*)gi + s * Tseq * N + nw + 16 * i + q4;
+            if (ta < Tseq) {
+                bf16x4_t o;
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    o[v] = (__bf16)__float2bfloat16(acc[i][0][v] +
+                                                    bias[i][v]);
+                *(bf16x4_t*)(gs + (long)ta * N) = o;
+            }
+            if (tb < Tseq) {
+                bf16x4_t o;
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    o[v] = (__bf16)__float2bfloat16(acc[i][1][v] +
+                                                    bias[i][v]);
+                *(bf16x4_t*)(gs + (long)tb * N) = o;
+            }
+        }
+    }
 }
 
 // Exact exchanges inside aligned groups of 8 lanes: lane l receives the
@@ -3617,6 +3805,45 @@ extern "C" int fmda_head_sigmoid_launch(int is_bf16, const void* x,
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// head_sigmoid over a bank of heads W (M, C, K), bias (M, C): row b uses
+// the head of slot[b]. Same lane-over-K sum and shuffle order as
+// head_sigmoid_kernel, so a row gets the bits that kernel gives with that
+// head alone.
+__global__ void head_sigmoid_bank_kernel(
+        const __hip_bfloat16* __restrict__ x, const int* __restrict__ slot,
+        const __hip_bfloat16* __restrict__ W,
+        const __hip_bfloat16* __restrict__ bias, float* __restrict__ probs,
+        int B, int K, int C, int M) {
+    using T = __hip_bfloat16;
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int idx = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (idx >= B * C) return;
+    const int b = idx / C, c = idx % C;
+    const long m = bank_slot(slot, b, M);
+    const T* xr = x + (long)b * K;
+    const T* wr = W + (m * C + c) * K;
+    float acc = 0.0f;
+    for (int k = lane; k < K; k += 64)
+        acc += to_f32<T>(xr[k]) * to_f32<T>(wr[k]);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) acc += __shfl_xor(acc, d);
+    if (lane == 0) probs[idx] = sigmoidf(acc + to_f32<T>(bias[m * C + c]));
+}
+
+extern "C" int fmda_head_sigmoid_bank_launch(const void* x, const int* slot,
+                                             const void* W, const void* bias,
+                                             float* probs, int B, int K,
+                                             int C, int M,
+                                             hipStream_t stream) {
+    if (B < 1 || K < 1 || C < 1 || M < 1) return -1;
+    const int n = B * C;
+    head_sigmoid_bank_kernel<<<dim3((n + 3) / 4), 256, 0, stream>>>(
+        (const __hip_bfloat16*)x, slot, (const __hip_bfloat16*)W,
+        (const __hip_bfloat16*)bias, probs, B, K, C, M);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ===========================================================================
 // Fused classifier head + BCEWithLogitsLoss (weight, pos_weight).
 // Replaces nn.Linear (biGRU_model.py:137) + the notebook's
@@ -4068,6 +4295,50 @@ extern "C" int fmda_gru_fwd_streams_launch(const void* gi, const void* w,
     k<<<dim3(n_dir, S), 256, lds, stream>>>(
         (const __hip_bfloat16*)gi, (const __hip_bfloat16*)w, bhh,
         (__hip_bfloat16*)out, hlast, Tseq, n_dir);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// The same launch over a bank of M models; slot is int32 (S) on the device.
+extern "C" int fmda_gru_fwd_streams_bank_launch(
+        const void* gi, const int* slot, int M, const void* w,
+        const float* bhh, void* out, float* hlast, int S, int Tseq,
+        int n_dir, hipStream_t stream) {
+    constexpr int Hp = 128;
+    const size_t lds = 2 * (size_t)Tseq * (3 * Hp + 8) + 2 * 2 * (Hp + 8) +
+                       4 * 3 * Hp;
+    if (lds > 150 * 1024) return -5;   // sequence too long for LDS residency
+    if (S < 1 || S > 65535 || M < 1) return -1;   // gridDim.y
+    auto k = gru_fwd_streams_bank_kernel<Hp, 256>;
+    (void)hipFuncSetAttribute((const void*)k,
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    k<<<dim3(n_dir, S), 256, lds, stream>>>(
+        (const __hip_bfloat16*)gi, slot, M, (const __hip_bfloat16*)w, bhh,
+        (__hip_bfloat16*)out, hlast, Tseq, n_dir);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// Grouped input projection; the load width follows what K and the base
+// pointers keep aligned (see gi_proj_bank_kernel).
+extern "C" int fmda_gi_proj_bank_launch(const void* x, const int* slot,
+                                        const void* W, const void* b,
+                                        void* gi, int S, int Tseq, int K,
+                                        int N, int M, hipStream_t stream) {
+    if (S < 1 || S > 65535 || Tseq < 1 || K < 1 || M < 1 || N < 16 ||
+        N % 16 != 0)
+        return -1;
+    if (((uintptr_t)gi & 7) != 0) return -1;     // 8-byte stores
+    const uintptr_t a = (uintptr_t)x | (uintptr_t)W;
+    const int row_tiles = (Tseq - 1) / 32 + 1;
+    if (row_tiles > 65535) return -1;            // gridDim.z
+    const dim3 grid((N + 255) / 256, S, row_tiles);
+#define FMDA_GI_BANK(VEC)                                                    \
+    gi_proj_bank_kernel<VEC><<<grid, 256, 0, stream>>>(                      \
+        (const __hip_bfloat16*)x, slot, (const __hip_bfloat16*)W,            \
+        (const __hip_bfloat16*)b, (__hip_bfloat16*)gi, Tseq, K, N, M)
+    if (K % 8 == 0 && (a & 15) == 0) FMDA_GI_BANK(8);
+    else if (K % 4 == 0 && (a & 7) == 0) FMDA_GI_BANK(4);
+    else FMDA_GI_BANK(1);
+#undef FMDA_GI_BANK
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -32,6 +32,7 @@ except ImportError:  # pragma: no cover
     _PROM = False
 
 from .runtime.fleet import FleetPredictor
+from .runtime.fleet_bank import BankedFleetPredictor
 from .runtime.streaming import StreamingPredictor
 
 
@@ -137,6 +138,11 @@ def create_fleet_app(predictor: FleetPredictor):
     - GET  /healthz                         -> symbols, window, device,
                                                per-symbol window_full
     - GET  /metrics                         -> Prometheus exposition
+
+    A BankedFleetPredictor (a bank of models, one slot per symbol) is
+    served unchanged and adds:
+    - POST /assign        {"symbol": s, "slot": k}  -> score s with model k
+    - GET  /healthz also reports the symbol -> slot map ("model_of")
     """
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import Response
@@ -203,16 +209,36 @@ def create_fleet_app(predictor: FleetPredictor):
                                 detail=f"unknown symbol {symbol!r}")
         return {"prediction": latest.get(symbol)}
 
+    banked = isinstance(predictor, BankedFleetPredictor)
+
     @app.get("/healthz")
     def healthz():
-        return {"ok": True,
-                "symbols": list(predictor.symbols),
-                "device": str(predictor.device),
-                "window": predictor.window,
-                "n_features": predictor.n_features,
-                "route": predictor.route,
-                "window_full": predictor.window_full(),
-                "n_predictions": predictor.n_predictions}
+        res = {"ok": True,
+               "symbols": list(predictor.symbols),
+               "device": str(predictor.device),
+               "window": predictor.window,
+               "n_features": predictor.n_features,
+               "route": predictor.route,
+               "window_full": predictor.window_full(),
+               "n_predictions": predictor.n_predictions}
+        if banked:
+            res["model_of"] = predictor.model_of()
+            res["n_models"] = len(predictor.models)
+        return res
+
+    if banked:
+        @app.post("/assign")
+        def assign(msg: dict):
+            if "symbol" not in msg or "slot" not in msg:
+                raise HTTPException(status_code=422,
+                                    detail="need symbol and slot")
+            try:
+                predictor.assign(msg["symbol"], msg["slot"])
+            except KeyError as e:
+                raise HTTPException(status_code=404, detail=str(e.args[0]))
+            except ValueError as e:
+                raise HTTPException(status_code=422, detail=str(e))
+            return {"ok": True, "model_of": predictor.model_of()}
 
     @app.get("/metrics")
     def metrics():
