@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "dropout_common.h"   // mix64, drop_hit, drop_apply
+#include "fmda_launch.h"
 
 #define FMDA_DEV __device__ __forceinline__
 

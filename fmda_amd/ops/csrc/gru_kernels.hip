@@ -11,11 +11,14 @@
 //   sequence: batch rows are independent, so there is no inter-workgroup
 //   communication and no grid sync. Both directions launch in one grid
 //   (blockIdx.y = direction).
-// - Recurrent-weight residency by size: for the hot configs (H = 128) the
-//   MFMA B-fragments of W_hh are HOISTED INTO REGISTERS once and live there
-//   across all T timesteps (HOIST; ~0.4-0.8 KB/lane) - zero W traffic in the
-//   loop. Small sizes keep W in LDS (WLDS); at H >= 256 W streams from the
-//   per-XCD L2.
+// - Recurrent-weight residency by size: the generic kernels keep W_hh in LDS
+//   at small sizes (WLDS) and stream it from the per-XCD L2 at H >= 256. The
+//   hot config (bf16 H = 128) runs the v3 kernels below, which hoist the
+//   MFMA B-fragments of W_hh INTO REGISTERS once for all T timesteps
+//   (~0.4-0.8 KB/lane) - zero W traffic in the loop.
+// - Each kernel's dynamic LDS layout is one constexpr struct (byte offset of
+//   every region and the total `bytes`): the kernel forms its pointers from
+//   it and the launcher sizes the launch from it.
 // - The next timestep's tiles are PREFETCHED into registers during the MFMA
 //   phase and committed to LDS after the barrier (async-STAGE split,
 //   cdna_hip_programming.md T14), so HBM latency hides under compute.
@@ -44,8 +47,10 @@
 #include <hip/hip_bf16.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "dropout_common.h"   // mix64, drop_hit, drop_apply
+#include "fmda_launch.h"
 
 #define FMDA_DEV __device__ __forceinline__
 
@@ -53,6 +58,16 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 namespace fmda {
+
+// The dynamic LDS of one CU; every layout struct asserts its total against it.
+constexpr int LDS_CU_BYTES = 160 * 1024;
+
+// Tile constants that fmda_gru_bwd_db_rows shares with the launchers that own
+// them: the v3 backward's batch tile, and the column-split kernels' batch
+// rows and block size.
+constexpr int BWD_V3_BT = 32;
+constexpr int CS_BR = 256;
+constexpr int CS_NT = 512;
 
 // Gate activations on the raw hardware transcendentals (v_exp_f32 computes
 // exp2; v_rcp_f32 is the fast reciprocal) — the libm expf/tanhf expansions
@@ -263,6 +278,44 @@ FMDA_DEV bf16x8_t load_wfragB(const __hip_bfloat16* __restrict__ w, long pitch,
     return b;
 }
 
+// Dynamic LDS of gru_fwd_kernel (byte offsets) and the padded pitches
+// (elements) of its tiles: W slice (WLDS only), fp32 h, bf16 h copy for the
+// MFMA A-fragments (bf16 only), gi tile, b_hh.
+template <typename T, int BT, int Hp, bool WLDS>
+struct FwdLds {
+    static constexpr int ES = (int)sizeof(T);
+    static constexpr int PADE = 16 / ES;
+    static constexpr int WP = Hp + PADE;
+    static constexpr int GP3 = 3 * Hp + PADE;
+    static constexpr int HFP = Hp + 4;
+    static constexpr int w = 0;
+    static constexpr int hf = w + (WLDS ? ES * 3 * Hp * WP : 0);
+    static constexpr int hb = hf + 4 * BT * HFP;
+    static constexpr int gi = hb + (ES == 2 ? 2 * BT * WP : 0);
+    static constexpr int bhh = gi + ES * BT * GP3;
+    static constexpr int bytes = bhh + 4 * 3 * Hp;
+    static_assert(bytes <= LDS_CU_BYTES, "forward tiles do not fit the LDS");
+};
+
+// Dynamic LDS of gru_bwd_kernel: W slice (WLDS only), fp32 dh carry, h_prev
+// tile, gi tile (turned into dGi in place), dGh tile, b_hh.
+template <typename T, int BT, int Hp, bool WLDS>
+struct BwdLds {
+    static constexpr int ES = (int)sizeof(T);
+    static constexpr int PADE = 16 / ES;
+    static constexpr int WP = Hp + PADE;
+    static constexpr int GP3 = 3 * Hp + PADE;
+    static constexpr int HFP = Hp + 4;
+    static constexpr int w = 0;
+    static constexpr int dh = w + (WLDS ? ES * 3 * Hp * WP : 0);
+    static constexpr int hb = dh + 4 * BT * HFP;
+    static constexpr int gi = hb + ES * BT * WP;
+    static constexpr int dgh = gi + ES * BT * GP3;
+    static constexpr int bhh = dgh + ES * BT * GP3;
+    static constexpr int bytes = bhh + 4 * 3 * Hp;
+    static_assert(bytes <= LDS_CU_BYTES, "backward tiles do not fit the LDS");
+};
+
 // ===========================================================================
 // Forward kernel.
 //
@@ -278,7 +331,7 @@ FMDA_DEV bf16x8_t load_wfragB(const __hip_bfloat16* __restrict__ w, long pitch,
 // hlast: (n_dir, B, Hp)     final hidden state (fp32)
 // grid:  (ceil(B/BT), n_dir); block NT threads; direction 1 runs reversed.
 // ===========================================================================
-template <typename T, int BT, int Hp, bool WLDS, int NT, bool HOIST>
+template <typename T, int BT, int Hp, bool WLDS, int NT>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                           amdgpu_waves_per_eu(NT / 256, NT / 256))) void gru_fwd_kernel(
     const T* __restrict__ gi, const T* __restrict__ w,
@@ -291,10 +344,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
     constexpr int CPW = (NCT + NW - 1) / NW;
     constexpr bool IS_BF16 = !__is_same(T, float);
     constexpr int KK = Hp / 32;
-    constexpr int PADE = 16 / (int)sizeof(T);
-    constexpr int WP = Hp + PADE;
-    constexpr int GP3 = 3 * Hp + PADE;
-    constexpr int HFP = Hp + 4;
+    using L = FwdLds<T, BT, Hp, WLDS>;
+    constexpr int WP = L::WP;
+    constexpr int GP3 = L::GP3;
+    constexpr int HFP = L::HFP;
     constexpr int GI_CHUNKS = (BT * 3 * Hp * (int)sizeof(T)) / 16;
     constexpr int PC = (GI_CHUNKS + NT - 1) / NT;
 
@@ -307,14 +360,12 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
     const int rows_valid = min(BT, B - b0);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* p = smem;
-    T* w_s = nullptr;
-    if (WLDS) { w_s = (T*)p; p += sizeof(T) * 3 * Hp * WP; }
-    float* hf_s = (float*)p; p += sizeof(float) * BT * HFP;
-    __hip_bfloat16* hb_s = nullptr;
-    if (IS_BF16) { hb_s = (__hip_bfloat16*)p; p += 2 * BT * WP; }
-    T* gi_s = (T*)p; p += sizeof(T) * BT * GP3;
-    float* bhh_s = (float*)p;
+    T* w_s = WLDS ? (T*)(smem + L::w) : nullptr;
+    float* hf_s = (float*)(smem + L::hf);
+    __hip_bfloat16* hb_s =
+        IS_BF16 ? (__hip_bfloat16*)(smem + L::hb) : nullptr;
+    T* gi_s = (T*)(smem + L::gi);
+    float* bhh_s = (float*)(smem + L::bhh);
 
     const T* wdir = w + (long)dir * 3 * Hp * Hp;
     if (WLDS)
@@ -346,22 +397,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
     const T* wfrag = WLDS ? w_s : wdir;
     const long wstride = WLDS ? WP : Hp;
 
-    // Hoist W B-fragments into registers for the whole sequence (bf16 only).
-    bf16x8_t wA[HOIST ? CPW : 1][3][HOIST ? KK : 1];
-    if constexpr (HOIST && IS_BF16) {
-#pragma unroll
-        for (int i = 0; i < CPW; ++i) {
-            const int ct = wave + NW * i;
-            if (ct >= NCT) continue;
-#pragma unroll
-            for (int g = 0; g < 3; ++g)
-#pragma unroll
-                for (int kk = 0; kk < KK; ++kk)
-                    wA[i][g][kk] = load_wfragA<Hp>(
-                        (const __hip_bfloat16*)wfrag, wstride, ct, g, kk,
-                        lane);
-        }
-    }
     __syncthreads();
 
     TilePrefetch<T, BT, NT, PC> pf;
@@ -371,7 +406,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
         // keep the L2-streamed W pointer opaque so the compiler does not
         // hoist every fragment load out of the loop and spill
         const T* wdyn = wfrag;
-        if constexpr (!WLDS && !HOIST && IS_BF16)
+        if constexpr (!WLDS && IS_BF16)
             asm volatile("" : "+s"(wdyn));
 
         // ---- phase A: issue next-step gi prefetch, then recurrent GEMM
@@ -405,11 +440,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                             (const __bf16*)hb_s)[(16 * m + arow) * WP + kbase];
 #pragma unroll
                     for (int g = 0; g < 3; ++g) {
-                        const bf16x8_t b =
-                            HOIST ? wA[i][g][kk]
-                                  : load_wfragA<Hp>(
-                                        (const __hip_bfloat16*)wdyn, wstride,
-                                        ct, g, kk, lane);
+                        const bf16x8_t b = load_wfragA<Hp>(
+                            (const __hip_bfloat16*)wdyn, wstride, ct, g, kk,
+                            lane);
 #pragma unroll
                         for (int m = 0; m < MT; ++m)
                             acc[i][g][m] =
@@ -504,7 +537,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
 // Backward (BPTT) kernel. See the header comment for the dGh time-shift and
 // the in-kernel db_hh reduction.
 // ===========================================================================
-template <typename T, int BT, int Hp, bool WLDS, int NT, bool HOIST>
+template <typename T, int BT, int Hp, bool WLDS, int NT>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                           amdgpu_waves_per_eu(NT / 256, NT / 256))) void gru_bwd_kernel(
     const T* __restrict__ gi, const T* __restrict__ w,
@@ -520,10 +553,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
     constexpr bool IS_BF16 = !__is_same(T, float);
     constexpr int KK = Hp / 32;
     constexpr int KK2 = (3 * Hp) / 32;
-    constexpr int PADE = 16 / (int)sizeof(T);
-    constexpr int WP = Hp + PADE;
-    constexpr int GP3 = 3 * Hp + PADE;
-    constexpr int HFP = Hp + 4;
+    using L = BwdLds<T, BT, Hp, WLDS>;
+    constexpr int WP = L::WP;
+    constexpr int GP3 = L::GP3;
+    constexpr int HFP = L::HFP;
     constexpr int GI_CHUNKS = (BT * 3 * Hp * (int)sizeof(T)) / 16;
     constexpr int H_CHUNKS = (BT * Hp * (int)sizeof(T)) / 16;
     constexpr int PCG = (GI_CHUNKS + NT - 1) / NT;
@@ -538,14 +571,12 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
     const int rows_valid = min(BT, B - b0);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* p = smem;
-    T* w_s = nullptr;
-    if (WLDS) { w_s = (T*)p; p += sizeof(T) * 3 * Hp * WP; }
-    float* dh_s = (float*)p; p += sizeof(float) * BT * HFP;
-    T* hb_s = (T*)p; p += sizeof(T) * BT * WP;
-    T* gi_s = (T*)p; p += sizeof(T) * BT * GP3;   // gi[t] -> dGi in place
-    T* dgh_s = (T*)p; p += sizeof(T) * BT * GP3;
-    float* bhh_s = (float*)p;
+    T* w_s = WLDS ? (T*)(smem + L::w) : nullptr;
+    float* dh_s = (float*)(smem + L::dh);
+    T* hb_s = (T*)(smem + L::hb);
+    T* gi_s = (T*)(smem + L::gi);   // gi[t] -> dGi in place
+    T* dgh_s = (T*)(smem + L::dgh);
+    float* bhh_s = (float*)(smem + L::bhh);
 
     const T* wdir = w + (long)dir * 3 * Hp * Hp;
     if (WLDS)
@@ -592,25 +623,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
     const T* wfrag = WLDS ? w_s : wdir;
     const long wstride = WLDS ? WP : Hp;
 
-    bf16x8_t wA[HOIST ? CPW : 1][3][HOIST ? KK : 1];
-    bf16x8_t wB[HOIST ? CPW : 1][HOIST ? KK2 : 1];
-    if constexpr (HOIST && IS_BF16) {
-#pragma unroll
-        for (int i = 0; i < CPW; ++i) {
-            const int ct = wave + NW * i;
-            if (ct >= NCT) continue;
-#pragma unroll
-            for (int g = 0; g < 3; ++g)
-#pragma unroll
-                for (int kk = 0; kk < KK; ++kk)
-                    wA[i][g][kk] = load_wfragA<Hp>(
-                        (const __hip_bfloat16*)wfrag, wstride, ct, g, kk, lane);
-#pragma unroll
-            for (int kk = 0; kk < KK2; ++kk)
-                wB[i][kk] = load_wfragB<Hp>((const __hip_bfloat16*)wfrag,
-                                            wstride, ct, kk, lane);
-        }
-    }
     __syncthreads();
 
     float dbacc[CPW][4];   // dr, dz, dhn (db_hh) + dn (db_ih n-slot)
@@ -629,7 +641,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
         const int un = u - 1;
         const int ttn = rev ? (Tseq - 1 - un) : un;
         const T* wdyn = wfrag;
-        if constexpr (!WLDS && !HOIST && IS_BF16)
+        if constexpr (!WLDS && IS_BF16)
             asm volatile("" : "+s"(wdyn));
 
         if (have_next) {
@@ -667,11 +679,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                             (const __bf16*)hb_s)[(16 * m + arow) * WP + kbase];
 #pragma unroll
                     for (int g = 0; g < 3; ++g) {
-                        const bf16x8_t b =
-                            HOIST ? wA[i][g][kk]
-                                  : load_wfragA<Hp>(
-                                        (const __hip_bfloat16*)wdyn, wstride,
-                                        ct, g, kk, lane);
+                        const bf16x8_t b = load_wfragA<Hp>(
+                            (const __hip_bfloat16*)wdyn, wstride, ct, g, kk,
+                            lane);
 #pragma unroll
                         for (int m = 0; m < MT; ++m)
                             acc[g][m] =
@@ -765,10 +775,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                         a[m] = *(const bf16x8_t*)&(
                             (const __bf16*)dgh_s)[(16 * m + arow) * GP3 +
                                                   kbase];
-                    const bf16x8_t b =
-                        HOIST ? wB[i][kk]
-                              : load_wfragB<Hp>((const __hip_bfloat16*)wdyn,
-                                                wstride, ct, kk, lane);
+                    const bf16x8_t b = load_wfragB<Hp>(
+                        (const __hip_bfloat16*)wdyn, wstride, ct, kk, lane);
 #pragma unroll
                     for (int m = 0; m < MT; ++m)
                         acc2[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -904,9 +912,23 @@ FMDA_DEV void glds16(const void* gsrc, void* ldst) {
         (__attribute__((address_space(3))) unsigned int*)ldst, 16, 0, 0);
 }
 
-// PHASES diagnostic mask like the backward's: 1 = recurrent GEMM,
-// 2 = gates. Production uses 3; other masks are timing-only.
-template <int BT, int Hp, int NT, int WPE, int PHASES = 3>
+// Dynamic LDS of gru_fwd_v3_kernel: the two-slot gi ring (unpadded rows, the
+// lane-linear image of the DMA), the double-buffered bf16 h tile at the
+// padded pitch WP (elements), b_hh.
+template <int BT, int Hp>
+struct FwdV3Lds {
+    static constexpr int GP = 3 * Hp;
+    static constexpr int WP = Hp + 8;
+    static constexpr int gi0 = 0;
+    static constexpr int gi1 = gi0 + 2 * BT * GP;
+    static constexpr int hb0 = gi1 + 2 * BT * GP;
+    static constexpr int hb1 = hb0 + 2 * BT * WP;
+    static constexpr int bhh = hb1 + 2 * BT * WP;
+    static constexpr int bytes = bhh + 4 * 3 * Hp;
+    static_assert(bytes <= LDS_CU_BYTES, "forward tiles do not fit the LDS");
+};
+
+template <int BT, int Hp, int NT, int WPE>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                           amdgpu_waves_per_eu(WPE, WPE)))
 void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
@@ -923,8 +945,9 @@ void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
     constexpr int NCT = Hp / 16;
     constexpr int CPW = NCT / NW;
     constexpr int KK = Hp / 32;
-    constexpr int GP = 3 * Hp;           // unpadded gi pitch (lane-linear DMA)
-    constexpr int WP = Hp + 8;           // padded bf16 h pitch
+    using L = FwdV3Lds<BT, Hp>;
+    constexpr int GP = L::GP;            // unpadded gi pitch (lane-linear DMA)
+    constexpr int WP = L::WP;            // padded bf16 h pitch
     constexpr int PIECES = (BT * GP * 2) / 1024;
     constexpr int PW = PIECES / NW;      // glds instructions per wave per step
     static_assert(PIECES % NW == 0 && NCT % NW == 0, "tiling mismatch");
@@ -938,17 +961,16 @@ void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
     const int rows_valid = min(BT, B - b0);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* p = smem;
     // Select HELPERS, not pointer arrays: a runtime-indexed local pointer
     // array defeats LDS address-space inference, so every gi/h access in
     // the loop compiled to FLAT ops — which wait on vmcnt and made the
     // compiler drain the in-flight LDS-DMA with a vmcnt(0) before every
     // gate group (the 2.4x slowdown this comment is a tombstone for).
-    __hip_bfloat16* gi_s0 = (__hip_bfloat16*)p; p += 2 * BT * GP;
-    __hip_bfloat16* gi_s1 = (__hip_bfloat16*)p; p += 2 * BT * GP;
-    __hip_bfloat16* hb_s0 = (__hip_bfloat16*)p; p += 2 * BT * WP;
-    __hip_bfloat16* hb_s1 = (__hip_bfloat16*)p; p += 2 * BT * WP;
-    float* bhh_s = (float*)p;
+    __hip_bfloat16* gi_s0 = (__hip_bfloat16*)(smem + L::gi0);
+    __hip_bfloat16* gi_s1 = (__hip_bfloat16*)(smem + L::gi1);
+    __hip_bfloat16* hb_s0 = (__hip_bfloat16*)(smem + L::hb0);
+    __hip_bfloat16* hb_s1 = (__hip_bfloat16*)(smem + L::hb1);
+    float* bhh_s = (float*)(smem + L::bhh);
     auto gi_buf = [&](int b) { return b ? gi_s1 : gi_s0; };
     auto hb_buf = [&](int b) { return b ? hb_s1 : hb_s0; };
 
@@ -1076,7 +1098,7 @@ void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
 #pragma unroll
                 for (int m = 0; m < MT; ++m) acc[i][g][m] = f32x4_t{0.f};
 #pragma unroll
-        for (int i = 0; PHASES & 1 && i < CPW; ++i) {
+        for (int i = 0; i < CPW; ++i) {
             const int arow = lane & 15;
             const int koff = 8 * (lane >> 4);
 #pragma unroll
@@ -1104,7 +1126,7 @@ void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
 
         // ---- phase B: fused gates; h stays in registers ----
 #pragma unroll
-        for (int i = 0; PHASES & 2 && i < CPW; ++i) {
+        for (int i = 0; i < CPW; ++i) {
             const int ct = wave + NW * i;
             const int j = ct * 16 + (lane & 15);
             const __bf16* gprow = (const __bf16*)gi_buf(pb);
@@ -1216,6 +1238,20 @@ void gru_fwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
 // MFMAs + one barrier per step per wave.
 // ===========================================================================
 
+// Dynamic LDS of gru_fwd_b1_body (byte offsets) for a sequence of Tseq
+// steps: the whole gi sequence at the padded row pitch GIP (elements), the
+// two-slot h ring (pitch HRP), b_hh. The same layout serves the batch-1,
+// streams and bank kernels.
+template <int Hp>
+struct B1Lds {
+    static constexpr int GIP = 3 * Hp + 8;
+    static constexpr int HRP = Hp + 8;
+    long gi, hr0, hr1, bhh, bytes;
+    __host__ __device__ constexpr explicit B1Lds(int Tseq)
+        : gi(0), hr0(gi + 2 * (long)Tseq * GIP), hr1(hr0 + 2 * HRP),
+          bhh(hr1 + 2 * HRP), bytes(bhh + 4 * 3 * Hp) {}
+};
+
 // One block's work, shared by the single-sequence kernel and the
 // multi-stream kernel below: direction blockIdx.x of ONE sequence. gi and
 // out point at that sequence's slab, h0 (or null) at its (n_dir, Hp)
@@ -1232,8 +1268,8 @@ void gru_fwd_b1_body(const __hip_bfloat16* __restrict__ gi,
     constexpr int CT = Hp / 16;      // 8 h-column tiles
     constexpr int CPW = CT / NW;     // 2 per wave
     constexpr int KK = Hp / 32;
-    constexpr int GIP = 3 * Hp + 8;  // padded gi row pitch (elements)
-    constexpr int HRP = Hp + 8;      // h ring pitch
+    constexpr int GIP = B1Lds<Hp>::GIP;  // padded gi row pitch (elements)
+    constexpr int HRP = B1Lds<Hp>::HRP;  // h ring pitch
     static_assert(CT % NW == 0, "tiling mismatch");
 
     const int tid = threadIdx.x;
@@ -1243,11 +1279,11 @@ void gru_fwd_b1_body(const __hip_bfloat16* __restrict__ gi,
     const bool rev = (dir == 1);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* p = smem;
-    __hip_bfloat16* gi_s = (__hip_bfloat16*)p; p += 2 * (long)Tseq * GIP;
-    __hip_bfloat16* hr0 = (__hip_bfloat16*)p; p += 2 * HRP;
-    __hip_bfloat16* hr1 = (__hip_bfloat16*)p; p += 2 * HRP;
-    float* bhh_s = (float*)p;
+    const B1Lds<Hp> L(Tseq);
+    __hip_bfloat16* gi_s = (__hip_bfloat16*)(smem + L.gi);
+    __hip_bfloat16* hr0 = (__hip_bfloat16*)(smem + L.hr0);
+    __hip_bfloat16* hr1 = (__hip_bfloat16*)(smem + L.hr1);
+    float* bhh_s = (float*)(smem + L.bhh);
     auto hring = [&](int s) { return s ? hr1 : hr0; };
 
     // stage the whole gi sequence (batch row 0, this direction); with a
@@ -1654,11 +1690,34 @@ FMDA_DEV void store_tile_pre(const char* __restrict__ lds,
     }
 }
 
-// PHASES: diagnostic bitmask (1 = recompute GEMM, 2 = gate grads,
-// 4 = carry GEMM). Production uses 7; other masks exist only so
-// scripts/kernel_micro.py can time each phase's contribution to the
-// serial chain by differencing (outputs are garbage for masks != 7).
-//
+// Dynamic LDS of gru_bwd_v3_kernel: the three-slot gi ring and the two h
+// tiles (unpadded rows: lane-linear DMA images), the d_out region, the
+// double-buffered dGh tile at the padded pitch GP3 (elements), b_hh. The
+// d_out region is two d_out tiles (do0, do1) in the dense kernel; the pooled
+// kernel keeps its (v0, v1) words in exactly that space (pv) and adds BT * Hp
+// amax bytes (im) behind it.
+template <int BT, int Hp, bool POOLED>
+struct BwdV3Lds {
+    static constexpr int GP = 3 * Hp;
+    static constexpr int HROW = Hp * 2;      // h/dout tile row bytes
+    static constexpr int GP3 = 3 * Hp + 8;
+    static constexpr int gi0 = 0;
+    static constexpr int gi1 = gi0 + 2 * BT * GP;
+    static constexpr int gi2 = gi1 + 2 * BT * GP;
+    static constexpr int hb0 = gi2 + 2 * BT * GP;
+    static constexpr int hb1 = hb0 + BT * HROW;
+    static constexpr int do0 = hb1 + BT * HROW;
+    static constexpr int pv = do0;
+    static constexpr int do1 = do0 + BT * HROW;
+    static constexpr int im = do1 + BT * HROW;
+    static constexpr int dgh0 = im + (POOLED ? BT * Hp : 0);
+    static constexpr int dgh1 = dgh0 + 2 * BT * GP3;
+    static constexpr int bhh = dgh1 + 2 * BT * GP3;
+    static constexpr int bytes = bhh + 4 * 3 * Hp;
+    static_assert(bytes <= LDS_CU_BYTES,
+                  "backward tiles / pooled table do not fit the LDS");
+};
+
 // POOLED: the layer feeds pool_features_fwd and nothing else, so its d_out
 // is never materialised. pool_features_bwd_kernel would write
 //   d_out[b, t, d*H + j] = bf16(ga + (t == amax[b, j] ? gm : 0.0f))
@@ -1677,8 +1736,7 @@ FMDA_DEV void store_tile_pre(const char* __restrict__ lds,
 // k * NT + tid of pv_s (v0 low half, v1 high half) and at byte e of word
 // (i * MT + m) * NT + tid of im_s: consecutive lanes read consecutive
 // words, and the offsets of k are immediates off one base register.
-template <int BT, int Hp, int NT, int WPE, int PHASES = 7,
-          bool POOLED = false>
+template <int BT, int Hp, int NT, int WPE, bool POOLED = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT),
                           amdgpu_waves_per_eu(WPE, WPE)))
 void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
@@ -1703,9 +1761,10 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
     constexpr int CPW = NCT / NW;
     constexpr int KK = Hp / 32;
     constexpr int KK2 = (3 * Hp) / 32;
-    constexpr int GP = 3 * Hp;
-    constexpr int HROW = Hp * 2;         // h/dout tile row bytes (unpadded)
-    constexpr int GP3 = 3 * Hp + 8;      // padded dgh_s pitch (MFMA A reads)
+    using L = BwdV3Lds<BT, Hp, POOLED>;
+    constexpr int GP = L::GP;
+    constexpr int HROW = L::HROW;        // h/dout tile row bytes (unpadded)
+    constexpr int GP3 = L::GP3;          // padded dgh_s pitch (MFMA A reads)
     constexpr int PW = (BT * GP * 2) / 1024 / NW;   // gi glds per wave
     constexpr int DOP = (BT * HROW) / 1024 / NW;    // dout glds per wave
     constexpr int HBP = DOP;                        // h glds per wave
@@ -1722,26 +1781,22 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
     const int rows_valid = min(BT, B - b0);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* p = smem;
     // Plain pointers + select helpers, NOT runtime-indexed local arrays:
     // a dynamically indexed private pointer array lands in scratch, and
     // every scratch reload is an ordinary VMEM load that triggers the
     // glds vmcnt(0) drain (this alone cost 3x on this kernel).
-    __hip_bfloat16* gi_s0 = (__hip_bfloat16*)p; p += 2 * BT * GP;
-    __hip_bfloat16* gi_s1 = (__hip_bfloat16*)p; p += 2 * BT * GP;
-    __hip_bfloat16* gi_s2 = (__hip_bfloat16*)p; p += 2 * BT * GP;
-    __hip_bfloat16* hb_s0 = (__hip_bfloat16*)p; p += BT * HROW;
-    __hip_bfloat16* hb_s1 = (__hip_bfloat16*)p; p += BT * HROW;
-    // dense: two d_out tiles (2 * BT * HROW bytes); pooled: the (v0, v1)
-    // words in exactly that space, then BT * Hp amax bytes
-    __hip_bfloat16* do_s0 = (__hip_bfloat16*)p;
-    unsigned int* pv_s = (unsigned int*)p; p += BT * HROW;
-    __hip_bfloat16* do_s1 = (__hip_bfloat16*)p; p += BT * HROW;
-    unsigned int* im_s = (unsigned int*)p;
-    if (POOLED) p += BT * Hp;
-    __hip_bfloat16* dgh_s0 = (__hip_bfloat16*)p; p += 2 * BT * GP3;
-    __hip_bfloat16* dgh_s1 = (__hip_bfloat16*)p; p += 2 * BT * GP3;
-    float* bhh_s = (float*)p;
+    __hip_bfloat16* gi_s0 = (__hip_bfloat16*)(smem + L::gi0);
+    __hip_bfloat16* gi_s1 = (__hip_bfloat16*)(smem + L::gi1);
+    __hip_bfloat16* gi_s2 = (__hip_bfloat16*)(smem + L::gi2);
+    __hip_bfloat16* hb_s0 = (__hip_bfloat16*)(smem + L::hb0);
+    __hip_bfloat16* hb_s1 = (__hip_bfloat16*)(smem + L::hb1);
+    __hip_bfloat16* do_s0 = (__hip_bfloat16*)(smem + L::do0);
+    __hip_bfloat16* do_s1 = (__hip_bfloat16*)(smem + L::do1);
+    unsigned int* pv_s = (unsigned int*)(smem + L::pv);
+    unsigned int* im_s = (unsigned int*)(smem + L::im);
+    __hip_bfloat16* dgh_s0 = (__hip_bfloat16*)(smem + L::dgh0);
+    __hip_bfloat16* dgh_s1 = (__hip_bfloat16*)(smem + L::dgh1);
+    float* bhh_s = (float*)(smem + L::bhh);
     auto dgh_buf = [&](int b) { return b ? dgh_s1 : dgh_s0; };
     auto gi_slot = [&](int sl) {
         return sl == 0 ? gi_s0 : (sl == 1 ? gi_s1 : gi_s2);
@@ -2069,7 +2124,7 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
 #pragma unroll
                 for (int m = 0; m < MT; ++m) acc[i][g][m] = f32x4_t{0.f};
 #pragma unroll
-        for (int i = 0; PHASES & 1 && i < CPW; ++i) {
+        for (int i = 0; i < CPW; ++i) {
             const int arow = lane & 15;
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
@@ -2090,7 +2145,7 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
             }
         }
 #pragma unroll
-        for (int i = 0; PHASES & 2 && i < CPW; ++i) {
+        for (int i = 0; i < CPW; ++i) {
             const int ct = wave + NW * i;
             const int j = ct * 16 + (lane & 15);
             __bf16* grow = (__bf16*)gi_slot(slot);
@@ -2199,7 +2254,7 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
         __builtin_amdgcn_s_barrier();
 
         // ---- phase C: carry GEMM dh += dGh W — registers + LDS only ----
-        if (PHASES & 4) {
+        {
             f32x4_t acc2[CPW][MT];
 #pragma unroll
             for (int i = 0; i < CPW; ++i)
@@ -2313,6 +2368,21 @@ void gru_bwd_v3_kernel(const __hip_bfloat16* __restrict__ gi,
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
+// Dynamic LDS of gru_fwd_cs_kernel and gru_bwd_cs_kernel (byte offsets): the
+// block's W_hh slice (3CS rows at the padded pitch WPITCH, elements), the
+// (BR, GP) gi tile that also stages the published strips, the block's b_hh.
+template <int BR, int Hp, int CS>
+struct CsLds {
+    static constexpr int WPITCH = Hp + 8;
+    static constexpr int GP = 3 * CS;
+    static constexpr int w = 0;
+    static constexpr int gi = w + 2 * 3 * CS * WPITCH;
+    static constexpr int bhh = gi + 2 * BR * GP;
+    static constexpr int bytes = bhh + 4 * 3 * CS;
+    static_assert(bytes <= LDS_CU_BYTES,
+                  "column-split tiles do not fit the LDS");
+};
+
 FMDA_DEV void store16_sc1(void* p, u32x4_t v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\ns_nop 1"
                  :: "v"(p), "v"(v) : "memory");
@@ -2337,8 +2407,8 @@ void gru_fwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
     constexpr int MT = BR / 16 / NW;     // m-tiles per wave
     constexpr int NCT = 3 * CS / 16;     // gate-column tiles (all per wave)
     constexpr int KK = Hp / 32;
-    constexpr int WPITCH = Hp + 8;       // W slice LDS pitch (elements)
-    constexpr int GP = 3 * CS;           // gi tile pitch (elements)
+    constexpr int WPITCH = CsLds<BR, Hp, CS>::WPITCH;  // W slice LDS pitch
+    constexpr int GP = CsLds<BR, Hp, CS>::GP;          // gi tile pitch
     static_assert(BR % (16 * NW) == 0, "rows must tile");
 
     const int tid = threadIdx.x;
@@ -2365,12 +2435,10 @@ void gru_fwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
     const int rows_valid = min(BR, B - b0);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* p = smem;
-    __hip_bfloat16* w_s = (__hip_bfloat16*)p;   // (3CS, WPITCH)
-    p += 2 * 3 * CS * WPITCH;
-    __hip_bfloat16* gi_s = (__hip_bfloat16*)p;  // (BR, GP), also h stage
-    p += 2 * BR * GP;
-    float* bhh_s = (float*)p;
+    using L = CsLds<BR, Hp, CS>;
+    __hip_bfloat16* w_s = (__hip_bfloat16*)(smem + L::w);    // (3CS, WPITCH)
+    __hip_bfloat16* gi_s = (__hip_bfloat16*)(smem + L::gi);  // also h stage
+    float* bhh_s = (float*)(smem + L::bhh);
 
     const long gi_row = gi_pitch;   // elements between batch rows of gi
     const long out_row = (long)Tseq * n_dir * Hp;
@@ -2614,10 +2682,9 @@ extern "C" int fmda_gru_fwd_cs_launch(const void* gi, const void* w,
                                       float drop_scale,
                                       unsigned long long drop_seed,
                                       long gi_pitch, hipStream_t stream) {
-    constexpr int BR = 256, Hp = 512, CS = 32, NT = 512;
+    constexpr int BR = CS_BR, Hp = 512, CS = 32, NT = CS_NT;
     const int GB = (B + BR - 1) / BR;
-    const size_t lds = 2 * 3 * CS * (Hp + 8) + 2 * (size_t)BR * 3 * CS +
-                       4 * 3 * CS;
+    constexpr size_t lds = CsLds<BR, Hp, CS>::bytes;
     auto k = gru_fwd_cs_kernel<BR, Hp, CS, NT>;
     (void)hipFuncSetAttribute((const void*)k,
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2672,8 +2739,8 @@ void gru_bwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
     constexpr int JT = CS / 16;          // 2 h-column tiles
     constexpr int KK = Hp / 32;          // 16 (recompute GEMM K)
     constexpr int KK2 = 3 * Hp / 32;     // 48 (carry GEMM K)
-    constexpr int WPITCH = Hp + 8;
-    constexpr int GP = 3 * CS;           // LDS gi/stage pitch
+    constexpr int WPITCH = CsLds<BR, Hp, CS>::WPITCH;
+    constexpr int GP = CsLds<BR, Hp, CS>::GP;          // LDS gi/stage pitch
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
@@ -2695,12 +2762,10 @@ void gru_bwd_cs_kernel(const __hip_bfloat16* __restrict__ gi,
     const int rows_valid = min(BR, B - b0);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* p = smem;
-    __hip_bfloat16* w_s = (__hip_bfloat16*)p;   // W_A slice (3CS, WPITCH)
-    p += 2 * 3 * CS * WPITCH;
-    __hip_bfloat16* gi_s = (__hip_bfloat16*)p;  // (BR, GP); also dGi/dGh stage
-    p += 2 * BR * GP;
-    float* bhh_s = (float*)p;
+    using L = CsLds<BR, Hp, CS>;
+    __hip_bfloat16* w_s = (__hip_bfloat16*)(smem + L::w);    // W_A slice
+    __hip_bfloat16* gi_s = (__hip_bfloat16*)(smem + L::gi);  // also dGi/dGh stage
+    float* bhh_s = (float*)(smem + L::bhh);
 
     const long gi_row = (long)Tseq * n_dir * 3 * Hp;
     const long out_row = (long)Tseq * n_dir * Hp;
@@ -3993,144 +4058,72 @@ __global__ void mfma_selftest_kernel(const __hip_bfloat16* __restrict__ A,
 // Host launchers.
 // ===========================================================================
 
-struct LaunchCfg { int bt; bool wlds; int nt; bool hoist; };
+// Tile / LDS-residency policy of the generic kernels, one row per (dtype, Hp)
+// they serve: X(is_bf16, Hp, BT, WLDS, NT). The forward dispatch, the
+// backward dispatch and the partials-table row count all expand this list.
+// bf16 Hp=128 is not here: it runs the v3 kernels.
+#define FMDA_GRU_GENERIC_ROWS(X)                                               \
+    X(1, 32, 32, true, 256)                                                    \
+    X(1, 64, 32, true, 256)                                                    \
+    X(1, 256, 32, false, 512)                                                  \
+    X(1, 512, 16, false, 512)                                                  \
+    X(0, 16, 32, false, 256)                                                   \
+    X(0, 32, 32, false, 256)                                                   \
+    X(0, 64, 32, false, 256)                                                   \
+    X(0, 128, 32, false, 256)                                                  \
+    X(0, 256, 16, false, 256)                                                  \
+    X(0, 512, 16, false, 256)
 
-// Tile/LDS/residency policy per (dtype, Hp); see header comment.
-static inline LaunchCfg fwd_cfg(bool bf16, int Hp) {
-    if (bf16) {
-        if (Hp <= 64) return {32, true, 256, false};
-        if (Hp == 128) return {32, false, 512, true};
-        if (Hp == 256) return {32, false, 512, false};
-        return {16, false, 512, false};
-    }
-    if (Hp <= 128) return {32, false, 256, false};
-    return {16, false, 256, false};
-}
-static inline LaunchCfg bwd_cfg(bool bf16, int Hp) {
-    if (bf16) {
-        if (Hp <= 64) return {32, true, 256, false};
-        if (Hp == 128) return {32, false, 512, true};
-        if (Hp == 256) return {32, false, 512, false};
-        return {16, false, 512, false};
-    }
-    if (Hp <= 128) return {32, false, 256, false};
-    return {16, false, 256, false};
-}
+template <int BF>
+using row_t = std::conditional_t<BF != 0, __hip_bfloat16, float>;
 
-// Mirrors the in-kernel padded pitches (WP/GP3/HFP).
-static inline size_t fwd_lds_bytes(bool bf16, int Hp, int bt, bool wlds) {
-    const size_t es = bf16 ? 2 : 4;
-    const size_t pade = 16 / es;
-    const size_t wp = Hp + pade, gp3 = 3 * Hp + pade, hfp = Hp + 4;
-    size_t s = 0;
-    if (wlds) s += es * 3 * Hp * wp;
-    s += 4 * (size_t)bt * hfp;
-    if (bf16) s += 2 * (size_t)bt * wp;
-    s += es * (size_t)bt * gp3;
-    s += 4 * (size_t)3 * Hp;
-    return s;
-}
-static inline size_t bwd_lds_bytes(bool bf16, int Hp, int bt, bool wlds) {
-    const size_t es = bf16 ? 2 : 4;
-    const size_t pade = 16 / es;
-    const size_t wp = Hp + pade, gp3 = 3 * Hp + pade, hfp = Hp + 4;
-    size_t s = 0;
-    if (wlds) s += es * 3 * Hp * wp;
-    s += 4 * (size_t)bt * hfp;
-    s += es * (size_t)bt * wp;
-    s += 2 * es * (size_t)bt * gp3;
-    s += 4 * (size_t)3 * Hp;
-    return s;
-}
-
-template <typename T, int BT, int Hp, bool WLDS, int NT, bool HOIST>
+template <typename T, int BT, int Hp, bool WLDS, int NT>
 static int launch_fwd(const void* gi, const void* w, const float* bhh,
                       void* out, float* hlast, int B, int Tseq, int n_dir,
-                      const float* h0, long gi_pitch, size_t lds,
-                      hipStream_t stream) {
-    auto k = gru_fwd_kernel<T, BT, Hp, WLDS, NT, HOIST>;
+                      const float* h0, long gi_pitch, hipStream_t stream) {
+    constexpr size_t lds = FwdLds<T, BT, Hp, WLDS>::bytes;
+    auto k = gru_fwd_kernel<T, BT, Hp, WLDS, NT>;
     (void)hipFuncSetAttribute((const void*)k,
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const dim3 grid((B + BT - 1) / BT, n_dir);
     k<<<grid, NT, lds, stream>>>((const T*)gi, (const T*)w, bhh, (T*)out,
                                  hlast, B, Tseq, n_dir, h0, gi_pitch);
-    return 0;
+    return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-template <typename T, int BT, int Hp, bool WLDS, int NT, bool HOIST>
+template <typename T, int BT, int Hp, bool WLDS, int NT>
 static int launch_bwd(const void* gi, const void* w, const float* bhh,
                       const void* out, const void* dout, const float* dhT,
                       void* dgi, void* dgh, float* dh0, float* dbhh, int B,
                       int Tseq, int n_dir, const float* h0, void* dgh0,
-                      size_t lds, hipStream_t stream) {
-    auto k = gru_bwd_kernel<T, BT, Hp, WLDS, NT, HOIST>;
-    (void)hipFuncSetAttribute((const void*)k,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const dim3 grid((B + BT - 1) / BT, n_dir);
-    k<<<grid, NT, lds, stream>>>((const T*)gi, (const T*)w, bhh,
-                                 (const T*)out, (const T*)dout, dhT, (T*)dgi,
-                                 (T*)dgh, dh0, dbhh, B, Tseq, n_dir, h0,
-                                 (T*)dgh0);
-    return 0;
+                      hipStream_t stream) {
+    // fp32 BPTT at Hp=512 would need ~264 KB of LDS: there is no such
+    // kernel, and the branch keeps the table's forward-only row from
+    // instantiating one.
+    if constexpr (sizeof(T) == 4 && Hp > 256) {
+        return -3;
+    } else {
+        constexpr size_t lds = BwdLds<T, BT, Hp, WLDS>::bytes;
+        auto k = gru_bwd_kernel<T, BT, Hp, WLDS, NT>;
+        (void)hipFuncSetAttribute((const void*)k,
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const dim3 grid((B + BT - 1) / BT, n_dir);
+        k<<<grid, NT, lds, stream>>>((const T*)gi, (const T*)w, bhh,
+                                     (const T*)out, (const T*)dout, dhT,
+                                     (T*)dgi, (T*)dgh, dh0, dbhh, B, Tseq,
+                                     n_dir, h0, (T*)dgh0);
+        return hipGetLastError() == hipSuccess ? 0 : -4;
+    }
 }
 
-using bf16_t = __hip_bfloat16;
-
-
-// v3 launch helpers (bf16 Hp=128).
+// Forward: BT=16 / NT=256, two 4-wave blocks per CU.
 static int launch_fwd_v3_128(const void* gi, const void* w, const float* bhh,
-                             void* out, float* hlast, int B, int Tseq,
-                             int n_dir, const float* h0, void* out_drop,
-                             unsigned int drop_thr, float drop_scale,
-                             unsigned long long drop_seed, long gi_pitch,
-                             hipStream_t stream) {
-    static const bool big = getenv("FMDA_FWD_BT32") != nullptr;
-    if (big) {   // A/B: one 8-wave block per CU instead of two 4-wave
-        constexpr int BT = 32, Hp = 128, NT = 512;
-        const size_t lds = 2 * 2 * BT * 3 * Hp + 2 * 2 * BT * (Hp + 8) +
-                           4 * 3 * Hp;
-        auto k2 = gru_fwd_v3_kernel<BT, Hp, NT, 2>;
-        (void)hipFuncSetAttribute((const void*)k2,
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        const dim3 grid((B + BT - 1) / BT, n_dir);
-        k2<<<grid, NT, lds, stream>>>((const __hip_bfloat16*)gi,
-                                      (const __hip_bfloat16*)w, bhh,
-                                      (__hip_bfloat16*)out, hlast, B, Tseq,
-                                      n_dir, h0, (__hip_bfloat16*)out_drop,
-                                      drop_thr, drop_scale, drop_seed,
-                                      gi_pitch);
-        return 0;
-    }
+                      void* out, float* hlast, int B, int Tseq, int n_dir,
+                      const float* h0, void* out_drop, unsigned int drop_thr,
+                      float drop_scale, unsigned long long drop_seed,
+                      long gi_pitch, hipStream_t stream) {
     constexpr int BT = 16, Hp = 128, NT = 256;
-    const size_t lds = 2 * 2 * BT * 3 * Hp + 2 * 2 * BT * (Hp + 8) +
-                       4 * 3 * Hp;
-    static const char* pm = getenv("FMDA_FWD_PHASES");
-    if (pm && atoi(pm) == 0) {   // timing-only skeleton (garbage output)
-        auto k0 = gru_fwd_v3_kernel<BT, Hp, NT, 2, 0>;
-        (void)hipFuncSetAttribute((const void*)k0,
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        const dim3 grid((B + BT - 1) / BT, n_dir);
-        k0<<<grid, NT, lds, stream>>>((const __hip_bfloat16*)gi,
-                                      (const __hip_bfloat16*)w, bhh,
-                                      (__hip_bfloat16*)out, hlast, B, Tseq,
-                                      n_dir, h0, (__hip_bfloat16*)out_drop,
-                                      drop_thr, drop_scale, drop_seed,
-                                      gi_pitch);
-        return 0;
-    }
-    if (pm && atoi(pm) == 1) {   // GEMM only, no gates
-        auto k1 = gru_fwd_v3_kernel<BT, Hp, NT, 2, 1>;
-        (void)hipFuncSetAttribute((const void*)k1,
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        const dim3 grid((B + BT - 1) / BT, n_dir);
-        k1<<<grid, NT, lds, stream>>>((const __hip_bfloat16*)gi,
-                                      (const __hip_bfloat16*)w, bhh,
-                                      (__hip_bfloat16*)out, hlast, B, Tseq,
-                                      n_dir, h0, (__hip_bfloat16*)out_drop,
-                                      drop_thr, drop_scale, drop_seed,
-                                      gi_pitch);
-        return 0;
-    }
+    constexpr size_t lds = FwdV3Lds<BT, Hp>::bytes;
     auto k = gru_fwd_v3_kernel<BT, Hp, NT, 2>;
     (void)hipFuncSetAttribute((const void*)k,
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -4140,25 +4133,24 @@ static int launch_fwd_v3_128(const void* gi, const void* w, const float* bhh,
                                  (__hip_bfloat16*)out, hlast, B, Tseq, n_dir,
                                  h0, (__hip_bfloat16*)out_drop, drop_thr,
                                  drop_scale, drop_seed, gi_pitch);
-    return 0;
+    return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-template <int BT, int NT, int PHASES = 7>
-static int launch_bwd_v3_128_t(const void* gi, const void* w, const void* wt,
-                               const float* bhh,
-                               const void* out, const void* dout,
-                               const float* dhT, void* dgi, void* dgh,
-                               float* dh0, float* dbhh, int B, int Tseq,
-                               int n_dir, unsigned int drop_thr,
-                               float drop_scale,
-                               unsigned long long drop_seed,
-                               const float* h0, void* dgh0,
-                               hipStream_t stream) {
-    constexpr int Hp = 128;
-    const size_t lds = 3 * 2 * BT * 3 * Hp + 2 * 2 * BT * Hp +
-                       2 * 2 * BT * Hp + 2 * 2 * BT * (3 * Hp + 8) +
-                       4 * 3 * Hp;
-    auto k = gru_bwd_v3_kernel<BT, Hp, NT, 2, PHASES>;
+// Backward: BT = BWD_V3_BT (32) / NT=512, one 8-wave block per CU. POOLED
+// takes d_out and d_hlast from dfeat (row pitch ld elements) and amax inside
+// the kernel, and dout / dhT / dropout from nowhere; dense takes no dfeat.
+template <bool POOLED>
+static int launch_bwd_v3(const void* gi, const void* w, const void* wt,
+                         const float* bhh, const void* out, const void* dout,
+                         const float* dhT, void* dgi, void* dgh, float* dh0,
+                         float* dbhh, int B, int Tseq, int n_dir,
+                         unsigned int drop_thr, float drop_scale,
+                         unsigned long long drop_seed, const float* h0,
+                         void* dgh0, const void* dfeat, const int* amax,
+                         long ld, hipStream_t stream) {
+    constexpr int BT = BWD_V3_BT, Hp = 128, NT = 512;
+    constexpr size_t lds = BwdV3Lds<BT, Hp, POOLED>::bytes;
+    auto k = gru_bwd_v3_kernel<BT, Hp, NT, 2, POOLED>;
     (void)hipFuncSetAttribute((const void*)k,
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const dim3 grid((B + BT - 1) / BT, n_dir);
@@ -4168,93 +4160,30 @@ static int launch_bwd_v3_128_t(const void* gi, const void* w, const void* wt,
         (const __hip_bfloat16*)out, (const __hip_bfloat16*)dout, dhT,
         (__hip_bfloat16*)dgi, (__hip_bfloat16*)dgh, dh0, dbhh, B, Tseq,
         n_dir, drop_thr, drop_scale, drop_seed, h0,
-        (__hip_bfloat16*)dgh0, nullptr, nullptr, 0L);
-    return 0;
-}
-
-// The POOLED variant of the BT=32 / NT=512 kernel: d_out and d_hlast come
-// from dfeat (row pitch ld elements) and amax inside the kernel. The two
-// 8 KB d_out tiles give way to the 16 KB + 4 KB table.
-static int launch_bwd_v3_128_pooled(const void* gi, const void* w,
-                                    const void* wt, const float* bhh,
-                                    const void* out, const void* dfeat,
-                                    const int* amax, long ld, void* dgi,
-                                    void* dgh, float* dh0, float* dbhh,
-                                    int B, int Tseq, int n_dir,
-                                    const float* h0, void* dgh0,
-                                    hipStream_t stream) {
-    constexpr int Hp = 128, BT = 32, NT = 512;
-    const size_t lds = 3 * 2 * BT * 3 * Hp + 2 * 2 * BT * Hp +
-                       (4 * BT * Hp + BT * Hp) + 2 * 2 * BT * (3 * Hp + 8) +
-                       4 * 3 * Hp;
-    static_assert(3 * 2 * BT * 3 * Hp + 2 * 2 * BT * Hp + 5 * BT * Hp +
-                  2 * 2 * BT * (3 * Hp + 8) + 4 * 3 * Hp <= 160 * 1024,
-                  "pooled table does not fit the LDS");
-    auto k = gru_bwd_v3_kernel<BT, Hp, NT, 2, 7, true>;
-    (void)hipFuncSetAttribute((const void*)k,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const dim3 grid((B + BT - 1) / BT, n_dir);
-    k<<<grid, NT, lds, stream>>>(
-        (const __hip_bfloat16*)gi, (const __hip_bfloat16*)w,
-        (const __hip_bfloat16*)wt, bhh,
-        (const __hip_bfloat16*)out, nullptr, nullptr,
-        (__hip_bfloat16*)dgi, (__hip_bfloat16*)dgh, dh0, dbhh, B, Tseq,
-        n_dir, 0u, 1.0f, 0ull, h0, (__hip_bfloat16*)dgh0,
-        (const __hip_bfloat16*)dfeat, amax, ld);
-    return 0;
-}
-
-// FMDA_BWD_BT16 A/B switch, latched once per process: the launcher's tile
-// size and the partials-table row count (fmda_gru_bwd_db_rows) both read it
-// here, so they can never disagree.
-static bool bwd_v3_bt16() {
-    static const bool small = getenv("FMDA_BWD_BT16") != nullptr;
-    return small;
+        (__hip_bfloat16*)dgh0, (const __hip_bfloat16*)dfeat, amax, ld);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 static int launch_bwd_v3_128(const void* gi, const void* w, const void* wt,
-                             const float* bhh,
-                             const void* out, const void* dout,
-                             const float* dhT, void* dgi, void* dgh,
-                             float* dh0, float* dbhh, int B, int Tseq,
-                             int n_dir, unsigned int drop_thr,
-                             float drop_scale, unsigned long long drop_seed,
-                             const float* h0, void* dgh0,
-                             hipStream_t stream) {
-    // A/B: BT=16/NT=256 runs TWO blocks per CU (like the forward) — two
-    // independent serial chains hide each other's latencies; MT=1 halves
-    // the per-lane accumulator footprint. ~80 KB dynamic LDS per block,
-    // 2x just fits the 160 KB CU budget.
-    if (bwd_v3_bt16())
-        return launch_bwd_v3_128_t<16, 256>(
-            gi, w, wt, bhh, out, dout, dhT, dgi, dgh, dh0, dbhh, B, Tseq,
-            n_dir, drop_thr, drop_scale, drop_seed, h0, dgh0, stream);
-    // diagnostic phase masks (outputs garbage; timing-only — see the
-    // kernel's PHASES comment)
-    static const char* pm = getenv("FMDA_BWD_PHASES");
-    if (pm) {
-        switch (atoi(pm)) {
-            case 6: return launch_bwd_v3_128_t<32, 512, 6>(
-                gi, w, wt, bhh, out, dout, dhT, dgi, dgh, dh0, dbhh, B,
-                Tseq, n_dir, drop_thr, drop_scale, drop_seed, h0, dgh0,
-                stream);
-            case 5: return launch_bwd_v3_128_t<32, 512, 5>(
-                gi, w, wt, bhh, out, dout, dhT, dgi, dgh, dh0, dbhh, B,
-                Tseq, n_dir, drop_thr, drop_scale, drop_seed, h0, dgh0,
-                stream);
-            case 3: return launch_bwd_v3_128_t<32, 512, 3>(
-                gi, w, wt, bhh, out, dout, dhT, dgi, dgh, dh0, dbhh, B,
-                Tseq, n_dir, drop_thr, drop_scale, drop_seed, h0, dgh0,
-                stream);
-            case 0: return launch_bwd_v3_128_t<32, 512, 0>(
-                gi, w, wt, bhh, out, dout, dhT, dgi, dgh, dh0, dbhh, B,
-                Tseq, n_dir, drop_thr, drop_scale, drop_seed, h0, dgh0,
-                stream);
-        }
-    }
-    return launch_bwd_v3_128_t<32, 512>(
-        gi, w, wt, bhh, out, dout, dhT, dgi, dgh, dh0, dbhh, B, Tseq,
-        n_dir, drop_thr, drop_scale, drop_seed, h0, dgh0, stream);
+                      const float* bhh, const void* out, const void* dout,
+                      const float* dhT, void* dgi, void* dgh, float* dh0,
+                      float* dbhh, int B, int Tseq, int n_dir,
+                      unsigned int drop_thr, float drop_scale,
+                      unsigned long long drop_seed, const float* h0,
+                      void* dgh0, hipStream_t stream) {
+    return launch_bwd_v3<false>(gi, w, wt, bhh, out, dout, dhT, dgi, dgh,
+                                dh0, dbhh, B, Tseq, n_dir, drop_thr,
+                                drop_scale, drop_seed, h0, dgh0, nullptr,
+                                nullptr, 0L, stream);
+}
+
+// Dynamic LDS of a batch-1 / streams / bank launch, or 0 when the sequence is
+// too long to stay LDS-resident (150 KB cap).
+template <int Hp>
+static size_t b1_lds_bytes(int Tseq) {
+    if (Tseq < 0) return 0;
+    const size_t lds = (size_t)B1Lds<Hp>(Tseq).bytes;
+    return lds > 150 * 1024 ? 0 : lds;
 }
 
 extern "C" int fmda_gru_fwd_b1_launch(const void* gi, const void* w,
@@ -4262,9 +4191,8 @@ extern "C" int fmda_gru_fwd_b1_launch(const void* gi, const void* w,
                                       float* hlast, int Tseq, int n_dir,
                                       const float* h0, hipStream_t stream) {
     constexpr int Hp = 128;
-    const size_t lds = 2 * (size_t)Tseq * (3 * Hp + 8) + 2 * 2 * (Hp + 8) +
-                       4 * 3 * Hp;
-    if (lds > 150 * 1024) return -5;   // sequence too long for LDS residency
+    const size_t lds = b1_lds_bytes<Hp>(Tseq);
+    if (lds == 0) return -5;   // sequence too long for LDS residency
     // A/B note: a 2-wave NT=128 variant (halved barrier width, CPW 4) was
     // measured 1.75x SLOWER — the doubled wA fragment hoist (192 VGPRs)
     // blows the register budget and the spill reloads dominate. 4 waves
@@ -4285,9 +4213,8 @@ extern "C" int fmda_gru_fwd_streams_launch(const void* gi, const void* w,
                                            float* hlast, int S, int Tseq,
                                            int n_dir, hipStream_t stream) {
     constexpr int Hp = 128;
-    const size_t lds = 2 * (size_t)Tseq * (3 * Hp + 8) + 2 * 2 * (Hp + 8) +
-                       4 * 3 * Hp;
-    if (lds > 150 * 1024) return -5;   // sequence too long for LDS residency
+    const size_t lds = b1_lds_bytes<Hp>(Tseq);
+    if (lds == 0) return -5;   // sequence too long for LDS residency
     if (S < 1 || S > 65535) return -1;   // gridDim.y
     auto k = gru_fwd_streams_kernel<Hp, 256>;
     (void)hipFuncSetAttribute((const void*)k,
@@ -4304,9 +4231,8 @@ extern "C" int fmda_gru_fwd_streams_bank_launch(
         const float* bhh, void* out, float* hlast, int S, int Tseq,
         int n_dir, hipStream_t stream) {
     constexpr int Hp = 128;
-    const size_t lds = 2 * (size_t)Tseq * (3 * Hp + 8) + 2 * 2 * (Hp + 8) +
-                       4 * 3 * Hp;
-    if (lds > 150 * 1024) return -5;   // sequence too long for LDS residency
+    const size_t lds = b1_lds_bytes<Hp>(Tseq);
+    if (lds == 0) return -5;   // sequence too long for LDS residency
     if (S < 1 || S > 65535 || M < 1) return -1;   // gridDim.y
     auto k = gru_fwd_streams_bank_kernel<Hp, 256>;
     (void)hipFuncSetAttribute((const void*)k,
@@ -4351,43 +4277,24 @@ extern "C" int fmda_gru_fwd_launch(int is_bf16, int Hp, const void* gi,
                                    long gi_pitch, hipStream_t stream) {
     if (out_drop != nullptr && !(is_bf16 && Hp == 128))
         return -6;   // fused fwd dropout only on the bf16 Hp=128 path
-    const LaunchCfg c = fwd_cfg(is_bf16, Hp);
-    const size_t lds = fwd_lds_bytes(is_bf16, Hp, c.bt, c.wlds);
-    if (lds > 160 * 1024) return -2;
-#define F(TY, BTV, HPV, WL, NTV, HO)                                           \
-    launch_fwd<TY, BTV, HPV, WL, NTV, HO>(gi, w, bhh, out, hlast, B, Tseq,     \
-                                          n_dir, h0, gi_pitch, lds, stream)
-    if (is_bf16) {
-        switch (Hp) {
-            case 16: return -7;   // KK = Hp/32 = 0: zero-trip MFMA loop
-            case 32: F(bf16_t, 32, 32, true, 256, false); break;
-            case 64: F(bf16_t, 32, 64, true, 256, false); break;
-            case 128:
-                if (B == 1 && out_drop == nullptr &&
-                    fmda_gru_fwd_b1_launch(gi, w, bhh, out, hlast, Tseq,
-                                           n_dir, h0, stream) == 0)
-                    break;   // LDS-resident batch-1 kernel took it
-                launch_fwd_v3_128(gi, w, bhh, out, hlast, B, Tseq, n_dir,
-                                  h0, out_drop, drop_thr, drop_scale,
-                                  drop_seed, gi_pitch, stream);
-                break;
-            case 256: F(bf16_t, 32, 256, false, 512, false); break;
-            case 512: F(bf16_t, 16, 512, false, 512, false); break;
-            default: return -1;
-        }
-    } else {
-        switch (Hp) {
-            case 16: F(float, 32, 16, false, 256, false); break;
-            case 32: F(float, 32, 32, false, 256, false); break;
-            case 64: F(float, 32, 64, false, 256, false); break;
-            case 128: F(float, 32, 128, false, 256, false); break;
-            case 256: F(float, 16, 256, false, 256, false); break;
-            case 512: F(float, 16, 512, false, 256, false); break;
-            default: return -1;
-        }
+    if (is_bf16 && Hp == 16)
+        return -7;   // KK = Hp/32 = 0: zero-trip MFMA loop
+    if (is_bf16 && Hp == 128) {
+        if (B == 1 && out_drop == nullptr &&
+            fmda_gru_fwd_b1_launch(gi, w, bhh, out, hlast, Tseq, n_dir, h0,
+                                   stream) == 0)
+            return 0;   // LDS-resident batch-1 kernel took it
+        return launch_fwd_v3_128(gi, w, bhh, out, hlast, B, Tseq, n_dir, h0,
+                                 out_drop, drop_thr, drop_scale, drop_seed,
+                                 gi_pitch, stream);
     }
-#undef F
-    return hipGetLastError() == hipSuccess ? 0 : -4;
+#define X(BF, HPV, BTV, WL, NTV)                                               \
+    if ((is_bf16 != 0) == (BF != 0) && Hp == HPV)                              \
+        return launch_fwd<row_t<BF>, BTV, HPV, WL, NTV>(                       \
+            gi, w, bhh, out, hlast, B, Tseq, n_dir, h0, gi_pitch, stream);
+    FMDA_GRU_GENERIC_ROWS(X)
+#undef X
+    return -1;
 }
 
 extern "C" int fmda_gru_bwd_cs_launch(const void* gi, const void* w,
@@ -4400,10 +4307,9 @@ extern "C" int fmda_gru_bwd_cs_launch(const void* gi, const void* w,
                                       float drop_scale,
                                       unsigned long long drop_seed,
                                       hipStream_t stream) {
-    constexpr int BR = 256, Hp = 512, CS = 32, NT = 512;
+    constexpr int BR = CS_BR, Hp = 512, CS = 32, NT = CS_NT;
     const int GB = (B + BR - 1) / BR;
-    const size_t lds = 2 * 3 * CS * (Hp + 8) + 2 * (size_t)BR * 3 * CS +
-                       4 * 3 * CS;
+    constexpr size_t lds = CsLds<BR, Hp, CS>::bytes;
     auto k = gru_bwd_cs_kernel<BR, Hp, CS, NT>;
     (void)hipFuncSetAttribute((const void*)k,
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -4419,14 +4325,18 @@ extern "C" int fmda_gru_bwd_cs_launch(const void* gi, const void* w,
 
 // Rows of the bias-grad partials table (rows, n_dir, 4Hp) that the backward
 // launch for this shape writes: one per batch tile (grid.x of the
-// batch-parallel kernels), or one per (256-row batch group, wave) for the
-// column-split kernel (BR = 256, NT = 512 -> 8 waves).
+// batch-parallel kernels), or one per (batch group, wave) for the
+// column-split kernel. 0 for a shape no backward kernel serves.
 extern "C" int fmda_gru_bwd_db_rows(int is_bf16, int Hp, int B,
                                     int column_split) {
-    if (column_split) return 8 * ((B + 255) / 256);
-    int bt = bwd_cfg(is_bf16, Hp).bt;
-    if (is_bf16 && Hp == 128 && bwd_v3_bt16()) bt = 16;
-    return (B + bt - 1) / bt;
+    if (column_split) return (CS_NT / 64) * ((B + CS_BR - 1) / CS_BR);
+    int bt = 0;
+    if (is_bf16 && Hp == 128) bt = BWD_V3_BT;
+#define X(BF, HPV, BTV, WL, NTV)                                               \
+    if ((is_bf16 != 0) == (BF != 0) && Hp == HPV) bt = BTV;
+    FMDA_GRU_GENERIC_ROWS(X)
+#undef X
+    return bt ? (B + bt - 1) / bt : 0;
 }
 
 // Sums the partials table (rows, n_dir, 4Hp) over rows in a fixed order and
@@ -4487,47 +4397,20 @@ extern "C" int fmda_gru_bwd_launch(int is_bf16, int Hp, const void* gi,
     if (!is_bf16 && Hp > 256) return -3;
     if (drop_thr != 0u && !(is_bf16 && Hp == 128))
         return -6;   // fused dropout-backward only on the bf16 Hp=128 path
-    const LaunchCfg c = bwd_cfg(is_bf16, Hp);
-    const size_t lds = bwd_lds_bytes(is_bf16, Hp, c.bt, c.wlds);
-    if (lds > 160 * 1024) return -2;
-#define G(TY, BTV, HPV, WL, NTV, HO)                                           \
-    launch_bwd<TY, BTV, HPV, WL, NTV, HO>(gi, w, bhh, out, dout, dhT, dgi,     \
-                                          dgh, dh0, dbhh, B, Tseq, n_dir,      \
-                                          h0, dgh0, lds, stream)
-    if (is_bf16) {
-        switch (Hp) {
-            case 16: return -7;   // KK = Hp/32 = 0: zero-trip MFMA loop
-            case 32: G(bf16_t, 32, 32, true, 256, false); break;
-            case 64: G(bf16_t, 32, 64, true, 256, false); break;
-            case 128:
-                launch_bwd_v3_128(gi, w, wt, bhh, out, dout, dhT, dgi, dgh,
-                                  dh0, dbhh, B, Tseq, n_dir, drop_thr,
-                                  drop_scale, drop_seed, h0, dgh0, stream);
-                break;
-            case 256: G(bf16_t, 32, 256, false, 512, false); break;
-            case 512: G(bf16_t, 16, 512, false, 512, false); break;
-            default: return -1;
-        }
-    } else {
-        switch (Hp) {
-            case 16: G(float, 32, 16, false, 256, false); break;
-            case 32: G(float, 32, 32, false, 256, false); break;
-            case 64: G(float, 32, 64, false, 256, false); break;
-            case 128: G(float, 32, 128, false, 256, false); break;
-            case 256: G(float, 16, 256, false, 256, false); break;
-            default: return -1;
-        }
-    }
-#undef G
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-
-// Whether this process launches the kernel that has a POOLED variant (the
-// v3 BT=32 / NT=512 one): not under the FMDA_BWD_BT16 / FMDA_BWD_PHASES
-// A/B switches, which are latched once per process like the launcher's.
-extern "C" int fmda_gru_bwd_pooled_available() {
-    static const bool phases = getenv("FMDA_BWD_PHASES") != nullptr;
-    return (bwd_v3_bt16() || phases) ? 0 : 1;
+    if (is_bf16 && Hp == 16)
+        return -7;   // KK = Hp/32 = 0: zero-trip MFMA loop
+    if (is_bf16 && Hp == 128)
+        return launch_bwd_v3_128(gi, w, wt, bhh, out, dout, dhT, dgi, dgh,
+                                 dh0, dbhh, B, Tseq, n_dir, drop_thr,
+                                 drop_scale, drop_seed, h0, dgh0, stream);
+#define X(BF, HPV, BTV, WL, NTV)                                               \
+    if ((is_bf16 != 0) == (BF != 0) && Hp == HPV)                              \
+        return launch_bwd<row_t<BF>, BTV, HPV, WL, NTV>(                       \
+            gi, w, bhh, out, dout, dhT, dgi, dgh, dh0, dbhh, B, Tseq, n_dir,   \
+            h0, dgh0, stream);
+    FMDA_GRU_GENERIC_ROWS(X)
+#undef X
+    return -1;
 }
 
 // Backward of a bf16 Hp=128 layer whose out feeds pool_features_fwd alone:
@@ -4542,11 +4425,10 @@ extern "C" int fmda_gru_bwd_pooled_launch(const void* gi, const void* w,
                                           int B, int Tseq, int n_dir,
                                           const float* h0, void* dgh0,
                                           hipStream_t stream) {
-    if (!fmda_gru_bwd_pooled_available()) return -8;
     if (Tseq < 1 || Tseq > 256 || ld < 3 * 128 || ld % 8 != 0) return -9;
-    launch_bwd_v3_128_pooled(gi, w, wt, bhh, out, dfeat, amax, ld, dgi, dgh,
-                             dh0, dbhh, B, Tseq, n_dir, h0, dgh0, stream);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
+    return launch_bwd_v3<true>(gi, w, wt, bhh, out, nullptr, nullptr, dgi,
+                               dgh, dh0, dbhh, B, Tseq, n_dir, 0u, 1.0f, 0ull,
+                               h0, dgh0, dfeat, amax, ld, stream);
 }
 
 extern "C" int fmda_mfma_selftest_launch(const void* A, const void* Bm,

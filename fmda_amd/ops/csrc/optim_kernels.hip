@@ -12,6 +12,8 @@
 // kernels do no searching.
 #include <hip/hip_runtime.h>
 
+#include "fmda_launch.h"
+
 namespace fmda {
 
 struct OptChunk {

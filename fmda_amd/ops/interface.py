@@ -719,11 +719,9 @@ def fused_pool_bwd_native(x: torch.Tensor, H: int) -> bool:
     features run as one node (_PooledFeatures' second form): the
     pooled_features_native
     conditions, H == Hp == 128, T <= 256 (amax travels as one byte),
-    training with grad enabled, the switch on, and the BPTT kernel that
-    has the variant selected."""
+    training with grad enabled, and the switch on."""
     return (_fused_pool_bwd() and pooled_features_native(x, H)
-            and H == 128 and x.shape[1] <= 256 and torch.is_grad_enabled()
-            and load_extension().gru_bwd_pooled_available())
+            and H == 128 and x.shape[1] <= 256 and torch.is_grad_enabled())
 
 
 

@@ -904,3 +904,78 @@ def test_fp32_h512_backward_raises_cleanly():
     import pytest as _pt
     with _pt.raises(RuntimeError, match="fp32 backward unsupported"):
         out.sum().backward()
+
+
+# One case per row of the launch table of the recurrence (gru_kernels.hip),
+# plus the v3 (bf16 Hp=128) and column-split (bf16 Hp=512, no h0) rows:
+# (dtype, Hp, B, h0, backward). B is that row's batch tile + 1: one full tile
+# and a one-row tail, so the bias-grad partials table has two rows and a row
+# count out of step with the launched tile shows up in db_hh. bf16 Hp=512
+# reaches its generic row only with an initial state; fp32 Hp=512 has no
+# backward.
+_DISPATCH_ROWS = [
+    ("bf16", 32, 33, False, True), ("bf16", 64, 33, False, True),
+    ("bf16", 128, 33, False, True), ("bf16", 256, 33, False, True),
+    ("bf16", 512, 17, True, True), ("bf16", 512, 257, False, True),
+    ("fp32", 16, 33, False, True), ("fp32", 32, 33, False, True),
+    ("fp32", 64, 33, False, True), ("fp32", 128, 33, False, True),
+    ("fp32", 256, 17, False, True), ("fp32", 512, 17, False, False),
+]
+
+
+@pytest.mark.parametrize("dtype,H,B,use_h0,bwd", _DISPATCH_ROWS)
+def test_gru_dispatch_table_rows(dtype, H, B, use_h0, bwd):
+    """Raw gru_fwd / gru_bwd bindings on every dispatch row vs the fp32
+    torch recurrence: out, hlast, dgi, the dgh-derived dW_hh, and db_hh.
+    Tolerances are those of the fp32 and bf16 tests above for the same
+    quantities."""
+    ext = _ext()
+    T, n_dir = 3, 2
+    torch.manual_seed(61)
+    gi = (torch.randn(B, T, n_dir * 3 * H) * 0.5).cuda()
+    w = (torch.randn(n_dir, 3 * H, H) * 0.2).cuda()
+    bhh = (torch.randn(n_dir, 3 * H) * 0.1).cuda()
+    h0 = (torch.randn(n_dir, B, H) * 0.5).cuda() if use_h0 else None
+    dO = torch.randn(B, T, n_dir * H).cuda()
+    dH = torch.randn(n_dir, B, H).cuda()
+    kd = torch.bfloat16 if dtype == "bf16" else torch.float32
+
+    gi_k, w_k = gi.to(kd), w.to(kd)
+    out, hlast = ext.gru_fwd(gi_k, w_k, bhh, h0)[:2]
+
+    gi2 = gi.clone().requires_grad_(True)
+    w2 = w.clone().requires_grad_(True)
+    b2 = bhh.clone().requires_grad_(True)
+    out_ref, hl_ref = _gru_ref_from_gi_autograd(gi2, w2, b2, h0)
+    if dtype == "fp32":
+        assert torch.allclose(out, out_ref, atol=1e-4), \
+            (out - out_ref).abs().max()
+        assert torch.allclose(hlast, hl_ref, atol=1e-4)
+    else:
+        assert (out.float() - out_ref).abs().max() < 0.05
+        assert (hlast - hl_ref).abs().max() < 0.05
+    if not bwd:
+        return
+
+    res = ext.gru_bwd(gi_k, w_k, bhh, out, dO.to(kd), dH, 0.0, 0, h0)
+    dgi, dgh, _dh0, dbhh = res[:4]
+    out_f, dgh_f = out.float(), dgh.float()
+    dw = torch.stack([
+        dgh_f[:, :, d * 3 * H:(d + 1) * 3 * H].reshape(-1, 3 * H).t()
+        @ out_f[:, :, d * H:(d + 1) * H].reshape(-1, H)
+        for d in range(n_dir)])
+    if use_h0:   # the t=0 term pairs with h0, not out
+        dw += torch.stack([res[5][d].float().t() @ h0[d]
+                           for d in range(n_dir)])
+    ((out_ref * dO).sum() + (hl_ref * dH).sum()).backward()
+    for nm, a, ref in [("dgi", dgi.float(), gi2.grad), ("dw_hh", dw, w2.grad),
+                       ("db_hh", dbhh, b2.grad)]:
+        if dtype == "fp32":
+            scale = ref.abs().max().clamp(min=1.0)
+            assert ((a - ref).abs().max() / scale) < 1e-4, nm
+        elif H <= 128:
+            rel = (a - ref).abs().max() / ref.abs().max().clamp(min=1e-2)
+            assert rel < 6e-2, f"{nm}: rel={rel}"
+        else:
+            rel = (a - ref).norm() / ref.norm().clamp(min=1e-2)
+            assert rel < 8e-2, f"{nm}: rel-L2={rel}"
